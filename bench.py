@@ -10,6 +10,12 @@ master weights, synthetic 28x28x1 data (60000 rows, no network), random-init wei
 Every timed step is a full training step: forward, loss, backward, RCCL all-reduce of
 the gradient (N > 1) and the SGD update (the last deferred update is flushed inside the
 timed region).  Run:  python bench.py --gpus N --steps K --warmup W
+Such a plain run sets up, warms up, times the K steps and prints one JSON line (``value``,
+``ms_per_step`` = milliseconds per timed step); ``--dump-outputs DIR`` also writes the
+weights and metrics the timed steps produced as DIR/<name>.npy (the seed is fixed, so two
+runs with the same arguments start from the same weights and see the same batches).
+Everything beyond the headline figure is opt-in: ``--phases``, ``--model``, ``--engine``;
+``--full`` is the switch for measurements a plain run would otherwise carry (none today).
 N > 1: either under ``python -m torch.distributed.run --nproc-per-node N ... bench.py``
 (RANK / WORLD_SIZE / MASTER_* in the environment), or plainly -- then this process
 spawns the N ranks itself (one child process per GPU, torchrun-style environment,
@@ -27,6 +33,36 @@ import time
 
 BASELINE_IMG_S = 6198.0  # reference 4-worker MWMS steady-state global rate (5,872-6,524)
 METRIC = "images/sec (whole node) MNIST CNN at 1/2/4/8 MI355X; DP scaling efficiency"
+BENCH_SEED = 20240607  # initial weights + epoch permutation of every run
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, model, metrics):
+    """Write what the timed steps computed to ``path``: every model weight after the last
+    timed step (``weight_<i>_<name>.npy``, float32, Keras weight order) and the running
+    loss / metrics over the steps run (``metrics.npy``, float64, with ``metrics_names.txt``).
+    If the weights exceed DUMP_LIMIT_BYTES in all, each array is cut to a fixed seeded sample
+    of its elements (the same elements in every run), in proportion."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    ws = model.weights
+    arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in model.get_weights()]
+    total = sum(a.nbytes for a in arrays)
+    budget = DUMP_LIMIT_BYTES - (1 << 20)  # room for the .npy headers and the metrics
+    rng = np.random.default_rng(BENCH_SEED)
+    for i, (w, a) in enumerate(zip(ws, arrays)):
+        if total > budget:
+            keep = max(1, int(a.size * budget / total))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=keep, replace=False))]
+        name = re.sub(r"[^A-Za-z0-9_.-]+", "_", str(getattr(w, "name", "") or "")).strip("_")
+        np.save(os.path.join(path, f"weight_{i:03d}_{name}.npy" if name else f"weight_{i:03d}.npy"), a)
+    names = sorted(k for k in metrics if not k.startswith("_"))
+    np.save(os.path.join(path, "metrics.npy"), np.array([metrics[k] for k in names], dtype=np.float64))
+    with open(os.path.join(path, "metrics_names.txt"), "w") as f:
+        f.write("\n".join(names) + "\n")
 
 
 def spawn_ranks(n: int, argv) -> int:
@@ -126,7 +162,16 @@ def main():
     ap.add_argument("--phases", type=int, default=0,
                     help="after the timed run, time N more eager steps phase by phase (forward / backward / "
                          "all-reduce / optimizer) and add them to the JSON line as phases_ms")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the model's weights after the last "
+                         "timed step and the epoch's loss / metrics) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (a plain run has none of its "
+                         "own: the per-phase times are asked for with --phases, other configurations with "
+                         "--model / --engine / --gpus)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     probes = sorted(k for k in os.environ if k.startswith("DAMD_PROBE_"))
     if probes:
@@ -163,6 +208,9 @@ def main():
             print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}; launch with torch.distributed.run",
                   file=sys.stderr)
             sys.exit(2)
+    # fixed seed: the initial weights (and the epoch permutation) are the same in every run
+    # with the same arguments, so the outputs of two builds compare array for array
+    tf.set_seed(BENCH_SEED)
     strategy = tf.distribute.experimental.MultiWorkerMirroredStrategy()
     rt = runtime.get()
     n = strategy.num_replicas_in_sync
@@ -296,6 +344,9 @@ def main():
     run(engine, args.warmup)
     engine.sync()
     dt, bar_s, ctl_in_window = timed(engine, args.steps, final)
+    if args.dump_outputs and rt.rank == 0:
+        # straight after the window, before any diagnostic step below moves the weights
+        dump_outputs(args.dump_outputs, model, engine.metrics())
     # diagnostics only (stderr, never the reported value): DAMD_BENCH_EXTRA=n repeats the
     # warmup + timed window n more times, to separate a first-window cost from the steady one
     for _ in range(int(os.environ.get("DAMD_BENCH_EXTRA", "0"))):

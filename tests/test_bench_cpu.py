@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,6 +67,43 @@ def test_bench_refuses_timing_probes():
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
     assert not lines
     assert "refusing" in r.stderr
+
+
+def _dump(d):
+    files = sorted(f for f in os.listdir(d) if f.endswith(".npy"))
+    return {f: np.load(os.path.join(d, f)) for f in files}
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR writes the weights after the last timed step (float32) and the
+    metrics (float64) as DIR/<name>.npy; the same arguments give the same arrays (fixed
+    seed, one thread: bitwise), another --steps gives other weights; --full is accepted and
+    leaves the result line's fields as they are."""
+    args = ["--gpus", "1", "--engine", "generic", "--warmup", "1"]
+    one = {"OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+    runs = []
+    for name, extra in (("a", ["--steps", "3"]), ("b", ["--steps", "3", "--full"]), ("c", ["--steps", "2"])):
+        r, lines = _run(args + extra + ["--dump-outputs", str(tmp_path / name)], one, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == int(extra[1]) and out["warmup"] == 1
+        assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "fp32"
+        assert out["ms_per_step"] > 0
+        assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) / out["value"] < 1e-3
+        runs.append((out, _dump(tmp_path / name)))
+    a, b, c = (d for _, d in runs)
+    ws = [k for k in a if k.startswith("weight_")]
+    assert [a[k].shape for k in ws] == [(3, 3, 1, 32), (32,), (5408, 64), (64,), (64, 10), (10,)]
+    assert all(a[k].dtype == np.float32 and np.isfinite(a[k]).all() for k in ws)
+    assert a["metrics.npy"].dtype == np.float64 and a["metrics.npy"].shape == (2,)
+    assert (tmp_path / "a" / "metrics_names.txt").read_text().split() == ["accuracy", "loss"]
+    assert abs(a["metrics.npy"][1] - runs[0][0]["final_epoch_loss"]) < 1e-4
+    assert list(a) == list(b) == list(c)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    # one step fewer: same start, other weights (the dump is the state after the LAST step)
+    assert any(not np.array_equal(a[k], c[k]) for k in ws)
 
 
 @pytest.mark.dist

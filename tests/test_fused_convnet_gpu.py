@@ -410,6 +410,57 @@ def test_final_graph_equals_run_then_flush(monkeypatch):
     assert res[0][1]["loss"] == res[1][1]["loss"] and res[0][1]["accuracy"] == res[1][1]["accuracy"]
 
 
+def test_bench_dump_outputs_are_the_timed_steps_weights(tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR --full``: the result line
+    keeps its fields, ``--steps`` is the number of timed steps, and the dumped float32
+    weights are bitwise those of the same seeded model after W + K steps and the flush, run
+    here through the engine directly (so the run's inputs are reproducible, too)."""
+    _need_gpu()
+    import json
+    import subprocess
+    import sys
+
+    import distributed_amd as tf
+
+    import bench  # (the repository root is on sys.path: tests/conftest.py)
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, W = 7, 5
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TF_CONFIG")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K),
+                        "--warmup", str(W), "--dump-outputs", str(d), "--full"], cwd=str(tmp_path), env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == K and out["warmup"] == W and out["config"]["engine"] == "fused_convnet"
+    assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["ms_per_step"] > 0
+    assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) / out["value"] < 1e-3
+    files = sorted(p for p in d.iterdir() if p.suffix == ".npy")
+    assert sum(p.stat().st_size for p in files) <= bench.DUMP_LIMIT_BYTES
+    ws = [np.load(p) for p in files if p.name.startswith("weight_")]
+    assert [w.shape for w in ws] == [(3, 3, 1, 32), (32,), (5408, 64), (64,), (64, 10), (10,)]
+    assert all(w.dtype == np.float32 for w in ws)
+    met = np.load(d / "metrics.npy")
+    assert met.dtype == np.float64 and (d / "metrics_names.txt").read_text().split() == ["accuracy", "loss"]
+    assert abs(met[1] - out["final_epoch_loss"]) < 1e-4
+    # the same W + K steps through the engine, from the same seed and data
+    tf.set_seed(bench.BENCH_SEED)
+    (x, y), _ = tf.keras.datasets.mnist.load_data()
+    x = x.reshape(len(x), 28, 28, 1) / 255.0
+    m = tf.models.mnist_cnn()
+    tf.models.compile_reference(m, 0.001)
+    eng = _engine(m, 64)
+    eng.bind(x, y)
+    eng.start_epoch(0, True, wrap_steps=len(x) // 64)
+    eng.run(W + K)
+    for a, b in zip(ws, m.get_weights()):
+        np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize("where", ["w1", "conv", "b1"])
 def test_nonfinite_weight_reports_nan_loss(where, monkeypatch):
     """the fixed-point cross-block sums cannot carry NaN / inf, so a non-finite
