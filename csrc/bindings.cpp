@@ -53,6 +53,7 @@ class ConvNetTrainer : public StepExecutor {
     b_.hconv = P_<long long>(g("hconv"));
     b_.calt = P_<float>(g("calt"));
     b_.ppb = bufs.contains("ppb") ? (int)g("ppb") : PP;
+    b_.force_generic = bufs.contains("specialised") ? !(int)g("specialised") : 0;
     // optional next-batch prefetch buffers (convnet.h): [B][784] x 4 bytes + one int64 tag
     b_.xnext = bufs.contains("xnext") ? P_<void>(g("xnext")) : nullptr;
     b_.xtag = bufs.contains("xtag") ? P_<long long>(g("xtag")) : nullptr;
@@ -196,6 +197,8 @@ class ConvNetTrainer : public StepExecutor {
   int num_slices() const { return convnet_num_slices(PP_); }
   int num_slices_bwd() const { return convnet_num_slices(b_.ppb); }
   int batch() const { return B_; }
+  // which instantiation of the step kernels a step launched now would run
+  std::string step_kernels() const { return convnet2_specialised(b_, B_, PP_) ? "specialised" : "generic"; }
 
  protected:
   void enqueue_tail() override { flush(); }
@@ -385,6 +388,7 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("num_slices", &ConvNetTrainer::num_slices)
       .def_property_readonly("num_slices_bwd", &ConvNetTrainer::num_slices_bwd)
       .def_property_readonly("batch", &ConvNetTrainer::batch)
+      .def_property_readonly("step_kernels", &ConvNetTrainer::step_kernels)
       .def_property_readonly("parity", &ConvNetTrainer::parity)
       .def_property_readonly("stream", [](ConvNetTrainer& t) { return reinterpret_cast<uintptr_t>(t.stream()); });
 

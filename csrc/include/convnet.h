@@ -77,6 +77,10 @@ struct ConvNetBuffers {
   // runs 4 image groups per slice (a 228-block grid at PP 3); the backward has one block per
   // slice, so a finer slicing spreads its dW1 / dP / conv-gradient work over more CUs
   int ppb;
+  // 1: always run the generic (runtime-size) step kernels, also at the flagship configuration
+  // that has constant-size instantiations (convnet2_specialised) -- for A/B runs on one build
+  // and the bitwise comparison of the two
+  int force_generic;
 };
 constexpr int kConvNetNConv = 320;
 constexpr int kConvNetNParam = 347146;
@@ -94,6 +98,8 @@ hipError_t convnet2_launch_flush(const ConvNetBuffers& b, int B, hipStream_t st)
 // sharded step: gather the pending update's reduced small gradients (before flush / host reads)
 hipError_t convnet2_launch_gather(const ConvNetBuffers& b, int PP, hipStream_t st);
 hipError_t convnet2_set_lds_limits();
+// true: a step with these buffers / sizes runs the constant-configuration kernels
+bool convnet2_specialised(const ConvNetBuffers& b, int B, int PP);
 // elements of the all-reduced gradient buffer
 size_t convnet_grad_count(int PP);
 }  // namespace damd

@@ -113,37 +113,75 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
                      bf2f((uint16_t)(q.y >> 16)));
 }
 
+// ---- compile-time configurations of the two step kernels -----------------------------
+// PP = 0: every size is a runtime value (the generic kernels: any B, any slicing, chunked
+// backward, deferred update, sharded exchange).  PP > 0: the sizes of one configuration are
+// constants -- LDS pitches and offsets become immediates, the slice loops have constant trip
+// counts and unroll, and the code of the paths the configuration never takes (deferred
+// update, sharded exchange, partial image groups) is not in the kernel at all.  Exactly one
+// such configuration exists per kernel: the world-1 step at 64 images per GPU with the
+// default slicing (fwd: 3 pooled positions per slice, 16 images per block; bwd: 2 positions,
+// single chunk), eager W1 update.  The last slice of either grid is shorter than PP
+// (NPOS = 169 = 56 * 3 + 1 = 84 * 2 + 1): it runs the same constant-trip code with the
+// operands of positions >= NPOS staged as zeros (0 x finite leaves the fp32 MFMA / fmaf sums
+// unchanged bit for bit) and their global loads, stores and atomics predicated off.
+struct CfgGeneric {
+  static constexpr int PP = 0, LG = 0;
+  static constexpr bool B64 = false, EAGER = false, SH = true;  // SH: may be sharded (xa.world)
+};
+struct CfgFlagFwd {
+  static constexpr int PP = 3, LG = 4;
+  static constexpr bool B64 = true, EAGER = true, SH = false;
+};
+struct CfgFlagBwd {
+  static constexpr int PP = 2, LG = 0;
+  static constexpr bool B64 = true, EAGER = true, SH = false;
+};
+// aux elements (b1/W2/b2 gradients + metric tail) per bwd block, and a power-of-two thread
+// count per element (<= 64) that fits them in 512 threads: chunk_aux | log2(threads) << 16
+__host__ __device__ constexpr int aux_split(int NS) {
+  const int chunk_aux = (NAUX2 + NS - 1) / NS;
+  int ltpe = 0;
+  while (ltpe < 6 && (2 << ltpe) * chunk_aux <= 512) ++ltpe;
+  return chunk_aux | (ltpe << 16);
+}
+
 // =================================================================================
 // fwd: grid (NS slices, IG image groups of IB = 2^lg images)
 // =================================================================================
-template <bool U8>
-// (ctrl and X lead the argument list: with kernarg preloading they arrive in SGPRs, so
-// the first dependent loads -- the ctrl block, then the batch rows -- start at once)
-// (the first 16 argument dwords arrive preloaded in SGPRs: the pointers of the prologue's
-// first loads and the packed sizes their addresses need -- bpp = B | PP << 16, lge = lg |
-// eager << 8; later arguments come from the kernarg segment, a scalar load's latency behind)
-__global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint16_t* __restrict__ w1bf,
-                                           float* __restrict__ P, float* __restrict__ V,
-                                           float* __restrict__ calt, const long long* __restrict__ hconv_r,
-                                           const float* __restrict__ G, int bpp, int lge, Ctrl* __restrict__ ctrl,
-                                           const void* __restrict__ X, float* __restrict__ W1alt,
-                                           float* __restrict__ V1alt, uint16_t* __restrict__ pooled,
-                                           uint8_t* __restrict__ code, long long* __restrict__ hacc,
-                                           long long* __restrict__ hconv, unsigned long long* st, const XArgs xa,
-                                           const long long* __restrict__ xtag, const int* __restrict__ labels,
-                                           void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
-  const int B = bpp & 0xffff, PP = bpp >> 16, lg = lge & 0xff, eager = lge >> 8;
+template <bool U8, class C>
+// (the body of both fwd kernels below: fwd, every size a runtime value, and fwd_flag, the
+// flagship configuration's constants folded -- bpp, lge and xa are not read there)
+__device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_t* __restrict__ w1bf,
+                                         float* __restrict__ P, float* __restrict__ V,
+                                         float* __restrict__ calt, const long long* __restrict__ hconv_r,
+                                         const float* __restrict__ G, int bpp, int lge, Ctrl* __restrict__ ctrl,
+                                         const void* __restrict__ X, float* __restrict__ W1alt,
+                                         float* __restrict__ V1alt, uint16_t* __restrict__ pooled,
+                                         uint8_t* __restrict__ code, long long* __restrict__ hacc,
+                                         long long* __restrict__ hconv, unsigned long long* st, const XArgs& xa,
+                                         const long long* __restrict__ xtag, const int* __restrict__ labels,
+                                         void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+  constexpr bool SPEC = C::PP > 0;
+  static_assert(!SPEC || (C::B64 && C::EAGER && !C::SH && C::LG == 4), "the one constant configuration");
+  const int B = SPEC ? CH : bpp & 0xffff, PP = SPEC ? C::PP : bpp >> 16, lg = SPEC ? C::LG : lge & 0xff;
+  const int eager = SPEC ? 1 : lge >> 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const bool sh = xa.world > 1;  // sharded multi-rank step: gradients from the exchange staging
+  const bool sh = C::SH && xa.world > 1;  // sharded multi-rank step: gradients from the exchange staging
   constexpr int hprobe = DAMD_PROBE_HACC;  // 0 in every product build (see the top of the file)
-  const int nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + s;
+  // (constant configuration: the grid is NS x B / IB blocks, every image group is full)
+  constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 0, IGC = SPEC ? CH >> C::LG : 0;
+  const int gx = SPEC ? NSC : (int)gridDim.x;
+  const int nblk = SPEC ? NSC * IGC : (int)(gridDim.x * gridDim.y), lin = blockIdx.y * gx + s;
   Stamps sts;
   stamp(sts, st, 0);
   const int IB = 1 << lg, img0 = blockIdx.y * IB;
   const int BP = (B + CH - 1) / CH * CH;
   const int p0 = s * PP, p1 = min(NPOS, p0 + PP), np = p1 - p0, K = np * 32;
   const int KP = kpitch(PP);
+  // trip count of the slice loops, pitch of the argmax-code tile: the constant PP, not np
+  const int npl = SPEC ? PP : np, KC = npl * 32;
   float* xs = reinterpret_cast<float*>(smem);                              // [IB][XR][28]; later [IB][64] partials
   uint16_t* as = reinterpret_cast<uint16_t*>(smem + IB * XR * IMG * 4);    // [IB][KP] pooled tile
   uint16_t* w1t = as + IB * KP;                                            // [HID][KP] W1 slice^T
@@ -156,7 +194,7 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
   XStage<U8> xst;
   long long xt = 0;
   if (xnext != nullptr) {
-    x_load<U8>(xst, xnext, img0, B, B - img0, lg, r0, nrows);
+    x_load<U8>(xst, xnext, img0, B, SPEC ? IB : B - img0, lg, r0, nrows);
     xt = *xtag;
   }
   // ---- first the loads whose addresses do not depend on the ctrl block: the bf16 W1 slice
@@ -206,7 +244,7 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
   // ---- then the ctrl-dependent loads: the batch rows unless prefetched (and, deferred
   // update, W1 by parity) ----
   const bool xhit = xnext != nullptr && xt == (((long long)c.xgen << 32) | (long long)(unsigned)(c.cursor + 1));
-  if (!xhit) x_load<U8>(xst, X, row_base, c.nsamples, B - img0, lg, r0, nrows);
+  if (!xhit) x_load<U8>(xst, X, row_base, c.nsamples, SPEC ? IB : B - img0, lg, r0, nrows);
   // this step's rows and labels for the backward (xcur / ycur): a share per block, from the
   // prefetch when it hit (L2-hot), else from the dataset; stored at the end of the kernel
   constexpr int UPI = U8 ? NPIX / 16 : NPIX / 4;  // 16-byte units per image
@@ -279,7 +317,9 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int i = tid + u * 512;  // 8 consecutive n of row kr
-      if (i < n4 / 2) {
+      // (constant configuration: every row of the tile is written -- the short last slice's
+      // rows past K with the zeros bq holds there, the dense-1 MFMAs run over all PP positions)
+      if (i < (SPEC ? PP * 32 * HID / 8 : n4 / 2)) {
         const int e = i * 8, kr = e >> 6, n = e & 63;
         const uint32_t w[4] = {bq[u].x, bq[u].y, bq[u].z, bq[u].w};
 #pragma unroll
@@ -346,10 +386,12 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
   ConvFrag cf;
   conv_setup(cf, cw, lane);
   stamp(sts, st, 5);
-  uint8_t* csl = reinterpret_cast<uint8_t*>(cw + NCONV);  // [IB][K] argmax codes
-  conv_pool(cf, xs, p0, np, r0, lg, wave, lane, [&](int bo, int plo, int ch, uint16_t hb, uint8_t cd) {
-    as[bo * KP + plo * 32 + ch] = hb;
-    csl[bo * K + plo * 32 + ch] = cd;
+  uint8_t* csl = reinterpret_cast<uint8_t*>(cw + NCONV);  // [IB][KC] argmax codes
+  conv_pool(cf, xs, p0, npl, r0, lg, wave, lane, [&](int bo, int plo, int ch, uint16_t hb, uint8_t cd) {
+    // (constant configuration: positions >= NPOS of the last slice were computed from rows
+    // nobody staged; their pooled value is 0, their code is never stored)
+    as[bo * KP + plo * 32 + ch] = SPEC && plo >= np ? (uint16_t)0 : hb;
+    csl[bo * KC + plo * 32 + ch] = cd;
   });
   stamp(sts, st, 6);
   lds_barrier();
@@ -357,13 +399,14 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
   // pooled tile (feature-major [k][b]: bwd's dW1 operand) and argmax codes ([b][k]) for
   // bwd, from LDS as contiguous 8-byte / 4-byte stores instead of scattered 1-2 B stores
   // (IB / 4 = 2^(lg - 2) and K / 4 = 8 np: shifts and a multiply, not divisions)
-  for (int i = tid; i < K * (IB / 4); i += 512) {
+  for (int i = tid; i < KC * (IB / 4); i += 512) {
+    if (SPEC && i >= K * (IB / 4)) break;
     const int kk = i >> (lg - 2), bo = 4 * (i & ((1 << (lg - 2)) - 1));
     uint16_t v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = as[(bo + e) * KP + kk];
     uint16_t* dst = pooled + (unsigned)((p0 * NF + kk) * BP + img0 + bo);
-    if (img0 + bo + 3 < B) {
+    if (SPEC || img0 + bo + 3 < B) {
       *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16),
                                                  (uint32_t)v[2] | ((uint32_t)v[3] << 16));
     } else {
@@ -372,11 +415,11 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
         if (img0 + bo + e < B) dst[e] = v[e];
     }
   }
-  for (int i = tid; i < IB * (K / 4); i += 512) {
-    const int i8 = i >> 3, bo = np == 3 ? (int)(((unsigned)i8 * 21846u) >> 16) : i8 >> (np >> 1), w = i - bo * (K / 4);
-    if (img0 + bo < B)
+  for (int i = tid; i < IB * (KC / 4); i += 512) {
+    const int i8 = i >> 3, bo = npl == 3 ? (int)(((unsigned)i8 * 21846u) >> 16) : i8 >> (npl >> 1), w = i - bo * (KC / 4);
+    if ((SPEC || img0 + bo < B) && (!SPEC || 4 * w < K))
       *reinterpret_cast<uint32_t*>(code + (unsigned)((img0 + bo) * FEAT + p0 * NF + 4 * w)) =
-          reinterpret_cast<const uint32_t*>(csl + bo * K)[w];
+          reinterpret_cast<const uint32_t*>(csl + bo * KC)[w];
   }
   stamp(sts, st, 7);
   if (sh) {
@@ -408,7 +451,7 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
     const int mt = t >> 2, nt = t & 3;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const int ar = 16 * mt + (lane & 15), bn = 16 * nt + (lane & 15);
-    for (int ks = 0; ks < np; ++ks) {
+    for (int ks = 0; ks < npl; ++ks) {
       const bf16x8 a = ld_frag(as + ar * KP + ks * 32 + ko);
       const bf16x8 bb = ld_frag(w1t + bn * KP + ks * 32 + ko);
       acc = mfma16(a, bb, acc);
@@ -422,12 +465,49 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
   // one wave instruction = one 512-B row of 64 int64 adds
   long long* hp = hacc + (long)par * B * HACC_PITCH;
   for (int r = wave; r < (hprobe == 1 ? 0 : hprobe == 2 ? IB / 2 : IB); r += 8)
-    if (img0 + r < B) atomic_add_i64(hp + (unsigned)((img0 + r) * HACC_PITCH + lane), to_fix(part[r * HID + lane], HSCALE, &ctrl->bad));
+    if (SPEC || img0 + r < B) atomic_add_i64(hp + (unsigned)((img0 + r) * HACC_PITCH + lane), to_fix(part[r * HID + lane], HSCALE, &ctrl->bad));
   if (xcp) reinterpret_cast<uint4*>(xcur)[xcu] = xcv;
   if (xcur != nullptr && lin == 0 && tid < B) ycur[tid] = ycv;
   stamp(sts, st, 4);
   if (st != nullptr && tid == 0 && lin < 256)
     for (int i = 0; i < 10; ++i) st[lin * 16 + i] = sts.t[i];
+}
+
+template <bool U8>
+// (ctrl and X lead the argument list: with kernarg preloading they arrive in SGPRs, so
+// the first dependent loads -- the ctrl block, then the batch rows -- start at once)
+// (the first 16 argument dwords arrive preloaded in SGPRs: the pointers of the prologue's
+// first loads and the packed sizes their addresses need -- bpp = B | PP << 16, lge = lg |
+// eager << 8; later arguments come from the kernarg segment, a scalar load's latency behind)
+__global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint16_t* __restrict__ w1bf,
+                                           float* __restrict__ P, float* __restrict__ V,
+                                           float* __restrict__ calt, const long long* __restrict__ hconv_r,
+                                           const float* __restrict__ G, int bpp, int lge, Ctrl* __restrict__ ctrl,
+                                           const void* __restrict__ X, float* __restrict__ W1alt,
+                                           float* __restrict__ V1alt, uint16_t* __restrict__ pooled,
+                                           uint8_t* __restrict__ code, long long* __restrict__ hacc,
+                                           long long* __restrict__ hconv, unsigned long long* st, const XArgs xa,
+                                           const long long* __restrict__ xtag, const int* __restrict__ labels,
+                                           void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+  fwd_body<U8, CfgGeneric>(xnext, w1bf, P, V, calt, hconv_r, G, bpp, lge, ctrl, X, W1alt, V1alt, pooled, code, hacc,
+                           hconv, st, xa, xtag, labels, xcur, ycur, phint);
+}
+
+// The flagship configuration (CfgFlagFwd): no packed sizes, no exchange arguments, no W1
+// double buffer (eager: fwd reads only the bf16 copy).  The preloaded 16 dwords are the
+// pointers of the loads issued ahead of the ctrl block, the prefetch tag among them.
+template <bool U8>
+__global__ __launch_bounds__(512) void fwd_flag(const void* __restrict__ xnext, const long long* __restrict__ xtag,
+                                                uint16_t* __restrict__ w1bf, float* __restrict__ P,
+                                                float* __restrict__ V, float* __restrict__ calt,
+                                                const long long* __restrict__ hconv_r, const float* __restrict__ G,
+                                                Ctrl* __restrict__ ctrl, const void* __restrict__ X,
+                                                uint16_t* __restrict__ pooled, uint8_t* __restrict__ code,
+                                                long long* __restrict__ hacc, long long* __restrict__ hconv,
+                                                unsigned long long* st, const int* __restrict__ labels,
+                                                void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+  fwd_body<U8, CfgFlagFwd>(xnext, w1bf, P, V, calt, hconv_r, G, 0, 0, ctrl, X, nullptr, nullptr, pooled, code, hacc,
+                           hconv, st, XArgs{}, xtag, labels, xcur, ycur, phint);
 }
 
 // =================================================================================
@@ -539,30 +619,36 @@ __device__ __forceinline__ void exchange_tail(const XArgs& xa, Ctrl* ctrl, const
 // =================================================================================
 // aux element e (parameter order at G + OFF_B1): [0,64) db1, [64,704) dW2
 // (k = (e-64)/10, c = (e-64)%10), [704,714) db2, then 714 loss, 715 correct, 716 count.
-template <bool U8, bool ONE>  // ONE: B <= 64, a single chunk (no loop-carried prefetch registers)
-// (the first 16 argument dwords arrive preloaded in SGPRs: they are what the prologue's first
-// loads address -- the dense-1 sums by the known parity, this step's staged labels / rows, b1 /
-// W2 / b2, the bf16 W1 slice, the pooled tile and codes; later arguments come from the
-// kernarg segment, a scalar load's latency behind)
-__global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const int* __restrict__ ycur,
-                                           const void* __restrict__ xcur, int phint, int bpp, const float* P,
-                                           const uint16_t* w1bf, const uint16_t* __restrict__ pooled,
-                                           const uint8_t* __restrict__ code, Ctrl* __restrict__ ctrl,
-                                           const void* __restrict__ X, const int* __restrict__ labels,
-                                           float* __restrict__ G, long long* __restrict__ hconv,
-                                           int eager, float* Pw, float* Vw, uint16_t* w1bf_out,
-                                           unsigned long long* st, const float* __restrict__ Gr, const XArgs xa,
-                                           void* __restrict__ xnext, long long* __restrict__ xtag, int auxm) {
-  const int B = bpp & 0xffff, PP = bpp >> 16;  // (packed: both preloaded)
+template <bool U8, bool ONE, class C>  // ONE: B <= 64, a single chunk (no loop-carried prefetch registers)
+// (the body of both bwd kernels below: bwd, every size a runtime value, and bwd_flag, the
+// flagship configuration's constants folded -- bpp, eager_, xa and auxm_ are not read there)
+__device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int* __restrict__ ycur,
+                                         const void* __restrict__ xcur, int phint, int bpp, const float* P,
+                                         const uint16_t* w1bf, const uint16_t* __restrict__ pooled,
+                                         const uint8_t* __restrict__ code, Ctrl* __restrict__ ctrl,
+                                         const void* __restrict__ X, const int* __restrict__ labels,
+                                         float* __restrict__ G, long long* __restrict__ hconv,
+                                         int eager_, float* Pw, float* Vw, uint16_t* w1bf_out,
+                                         unsigned long long* st, const float* __restrict__ Gr, const XArgs& xa,
+                                         void* __restrict__ xnext, long long* __restrict__ xtag, int auxm_) {
+  constexpr bool SPEC = C::PP > 0;
+  static_assert(!SPEC || (ONE && C::B64 && C::EAGER && !C::SH), "the one constant configuration");
+  const int B = SPEC ? CH : bpp & 0xffff, PP = SPEC ? C::PP : bpp >> 16;  // (packed: both preloaded)
+  const int eager = SPEC ? 1 : eager_;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const bool sh = xa.world > 1;  // sharded multi-rank step (see the exchange at the end)
+  const bool sh = C::SH && xa.world > 1;  // sharded multi-rank step (see the exchange at the end)
   constexpr int cprobe = DAMD_PROBE_HCONV;  // 0 in every product build (see the top of the file)
   Stamps sts;
   stamp(sts, st, 0);
-  const int s = blockIdx.x, tid = threadIdx.x, NS = gridDim.x;
+  constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 1;  // (constant configuration: the grid)
+  const int s = blockIdx.x, tid = threadIdx.x, NS = SPEC ? NSC : (int)gridDim.x;
+  const int auxm = SPEC ? aux_split(NSC) : auxm_;
   const int p0 = s * PP, p1 = min(NPOS, p0 + PP), np = p1 - p0, K = np * 32;
   const int KD = PP * 32 + 4;   // dps pitch (f32)
   const int KC = PP * 32;       // code pitch (bytes)
+  // trip count of the slice loops: the constant PP, not np (short last slice: zero operands,
+  // global loads / stores predicated off)
+  const int npl = SPEC ? PP : np;
   const int RB = max(CH * KD * 4, HEAD_BYTES);
   float* xs = reinterpret_cast<float*>(smem);                              // [CH][XR][28]
   float* dps = reinterpret_cast<float*>(smem + XS_BYTES);                  // [CH][KD] (after the head)
@@ -625,7 +711,8 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
   // (conditional loads, not selects between pointers: see fwd's bq)
   wv0 = wv1 = make_uint4(0u, 0u, 0u, 0u);
   if (tid < n8) wv0 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid];
-  if (tid + 512 < n8) wv1 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + 512];
+  if ((!SPEC || 512 < PP * 32 * HID / 8) && tid + 512 < n8)
+    wv1 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + 512];
   // the body -- pooled tile, argmax codes, input rows, read only by the MFMAs and the conv
   // gradient -- is staged by NB threads with two slots each: all 512 when chunked; in the
   // single-chunk step only waves 4-7 (slots bt and bt + 256), which have no logits to
@@ -642,6 +729,8 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
   bool yval = false;
   const int BP = (B + CH - 1) / CH * CH;
   const int kc = K / 16;  // = 2 np, np in 1..MAXPP
+  // (constant configuration) pooled-tile slots a body thread needs, 16-byte code units per image
+  constexpr int NPV = SPEC ? (C::PP * 32 * 8 + NB - 1) / NB : 4, KCM = SPEC ? 2 * C::PP : 1;
   // i / kc for i < 512 without a division sequence: (i / 2) / np, np = 3 by a multiply
   auto div_kc = [&](int i) __attribute__((always_inline)) {
     return np == 3 ? (int)(((unsigned)(i >> 1) * 21846u) >> 16) : (i >> 1) >> (np >> 1);
@@ -653,7 +742,16 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     v = make_uint4(0u, 0u, 0u, 0u);
     if (i < K * 8) v = *reinterpret_cast<const uint4*>(pooled + (__umul24(p0 * NF + (i >> 3), BP) + chunk * CH + (i & 7) * 8));
   };
+  // (constant configuration: unit i = image i / KCM, 16 codes q = i % KCM; units past the
+  // short last slice are not loaded and staged as zeros)
   auto load_cv = [&](uint4& v, bool& ok, int i, int chunk) __attribute__((always_inline)) {
+    if constexpr (SPEC) {
+      const int bb = i / KCM, q = i - bb * KCM;
+      ok = i < CH * KCM && q < kc;
+      v = make_uint4(0u, 0u, 0u, 0u);
+      if (ok) v = *reinterpret_cast<const uint4*>(code + (__umul24(bb, FEAT) + p0 * NF + q * 16));
+      return;
+    }
     const int bb = div_kc(i), q = i - bb * kc, lb = chunk * CH + bb;
     ok = i < CH * kc && lb < B;
     v = make_uint4(0u, 0u, 0u, 0u);
@@ -663,12 +761,12 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     if (bw) {
       load_pv(pv0, bt, chunk);
       load_pv(pv1, bt + NB, chunk);
-      if (ONE) {
+      if (ONE && NPV > 2) {
         load_pv(pv2, bt + 2 * NB, chunk);
         load_pv(pv3, bt + 3 * NB, chunk);
       }
       load_cv(cv, cok, bt, chunk);
-      if (ONE) load_cv(cv1, cok1, bt + NB, chunk);
+      if (ONE && (!SPEC || NB < CH * KCM)) load_cv(cv1, cok1, bt + NB, chunk);
     }
     if (ycur != nullptr) {  // labels and rows as this step's fwd read them: no cursor needed
       const int b = chunk * CH + min(tid, CH - 1);
@@ -738,9 +836,15 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     if (tid < CH) ylds[tid] = yval ? ylab : -1;
   };
   auto store_pv = [&](const uint4& v, int i) __attribute__((always_inline)) {
-    if (i < K * 8) *reinterpret_cast<uint4*>(pt + (i >> 3) * HP + (i & 7) * 8) = v;
+    // (constant configuration: every row of the tile, rows past K as the zeros loaded)
+    if (i < (SPEC ? PP * 32 * 8 : K * 8)) *reinterpret_cast<uint4*>(pt + (i >> 3) * HP + (i & 7) * 8) = v;
   };
   auto store_cv = [&](const uint4& v, bool ok, int i) __attribute__((always_inline)) {
+    if constexpr (SPEC) {
+      const int bb = i / KCM, q = i - bb * KCM;
+      if (i < CH * KCM) *reinterpret_cast<uint4*>(cs + bb * KC + q * 16) = ok ? v : make_uint4(0u, 0u, 0u, 0u);
+      return;
+    }
     if (i < CH * kc) {
       const int bb = div_kc(i), q = i - bb * kc;
       *reinterpret_cast<uint4*>(cs + bb * KC + q * 16) = ok ? v : make_uint4(0u, 0u, 0u, 0u);
@@ -750,12 +854,12 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     if (!bw) return;
     store_pv(pv0, bt);
     store_pv(pv1, bt + NB);
-    if (ONE) {
+    if (ONE && NPV > 2) {
       store_pv(pv2, bt + 2 * NB);
       store_pv(pv3, bt + 3 * NB);
     }
     store_cv(cv, cok, bt);
-    if (ONE) store_cv(cv1, cok1, bt + NB);
+    if (ONE && (!SPEC || NB < CH * KCM)) store_cv(cv1, cok1, bt + NB);
     x_store<U8>(xst, xs, LG_CH, nrows);
     if (ONE) x_store<U8>(xst1, xs, LG_CH, nrows);
   };
@@ -772,8 +876,10 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
       xnv = reinterpret_cast<const uint4*>(static_cast<const char*>(X) + __umul24((unsigned)g, U8 ? NPIX : 4 * NPIX))[q];
   }
   // (w1s is read only by the dP MFMAs, several barriers later)
-  if (tid < n8) *reinterpret_cast<uint4*>(w1s + (tid >> 3) * HP + (tid & 7) * 8) = wv0;
-  if (tid + 512 < n8) *reinterpret_cast<uint4*>(w1s + ((tid + 512) >> 3) * HP + (tid & 7) * 8) = wv1;
+  // (constant configuration: every row of the tile is written, rows past K as the zeros held)
+  const int n8s = SPEC ? PP * 32 * HID / 8 : n8;
+  if (tid < n8s) *reinterpret_cast<uint4*>(w1s + (tid >> 3) * HP + (tid & 7) * 8) = wv0;
+  if (tid + 512 < n8s) *reinterpret_cast<uint4*>(w1s + ((tid + 512) >> 3) * HP + (tid & 7) * 8) = wv1;
 
   const int dn = wave & 3, dm0 = wave >> 2;
   const bool mom = c.momentum != 0.f;
@@ -821,7 +927,8 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     if (ONE && eager) {
 #pragma unroll
       for (int i = 0; i < MAXPP; ++i) {
-        if (i >= np) break;
+        if (i >= npl) break;
+        if (SPEC && i >= np) continue;  // (short last slice: nothing to update)
         const int mt = dm0 + 2 * i;
         // (one address per tile, the 4 rows at immediate offsets)
         const unsigned e0 = OFF_W1 + (unsigned)((p0 * 32 + 16 * mt + 4 * (lane >> 4)) * HID + 16 * dn + lr16);
@@ -982,7 +1089,7 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     // dW1[k][n] += sum_b P[b][k] (dh_hi + dh_lo)[b][n]
 #pragma unroll
     for (int i = 0; i < MAXPP; ++i) {
-      if (i >= np) break;
+      if (i >= npl) break;
       const int mt = dm0 + 2 * i;
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
@@ -1002,7 +1109,8 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
     if (ONE && eager) {
 #pragma unroll
       for (int i = 0; i < MAXPP; ++i) {
-        if (i >= np) break;
+        if (i >= npl) break;
+        if (SPEC && i >= np) continue;
         const int mt = dm0 + 2 * i;
         const unsigned e0 = OFF_W1 + (unsigned)((p0 * 32 + 16 * mt + 4 * (lane >> 4)) * HID + 16 * dn + lr16);
         float* pw = Pw + e0;
@@ -1023,7 +1131,7 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
       const int pm = wave & 3;
 #pragma unroll
       for (int i = 0; i < MAXPP; ++i) {
-        if (i >= np) break;
+        if (i >= npl) break;
         const int nt = (wave >> 2) + 2 * i;
         f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1044,7 +1152,9 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
       const int bb = grp * 4 + ii;
-      for (int pl = 0; pl < np; ++pl) {
+      for (int pl = 0; pl < npl; ++pl) {
+        // (short last slice: the rows of a position >= NPOS were never staged -- no 0 x garbage)
+        if (SPEC && pl >= np) continue;
         const int cd = cs[bb * KC + pl * 32 + ch];
         const int pos = p0 + pl, py = pos / PO, px = pos - py * PO;
         const float dv0 = dps[bb * KD + pl * 32 + ch];
@@ -1116,10 +1226,45 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
   }
   if (xpf) reinterpret_cast<uint4*>(xnext)[xpu] = xnv;
   if (ONE && xnext != nullptr && s == 0 && tid == 0) *xtag = ((long long)c.xgen << 32) | (long long)(unsigned)(ncur + 1);
-  if (sh) exchange_tail(xa, ctrl, G, hconv + par * NCONV, accw, xe, s, NS, np, p0, dn, dm0, lane, tid, xown, xo, xu);
+  if (C::SH && sh) exchange_tail(xa, ctrl, G, hconv + par * NCONV, accw, xe, s, NS, np, p0, dn, dm0, lane, tid, xown, xo, xu);
   stamp(sts, st, 5);
   stamp_flush(sts, st, 13);
   if (st != nullptr && tid == 256) st[blockIdx.x * 16 + 13] = sts.t[12];  // wave 4's view
+}
+
+template <bool U8, bool ONE>
+// (the first 16 argument dwords arrive preloaded in SGPRs: they are what the prologue's first
+// loads address -- the dense-1 sums by the known parity, this step's staged labels / rows, b1 /
+// W2 / b2, the bf16 W1 slice, the pooled tile and codes; later arguments come from the
+// kernarg segment, a scalar load's latency behind)
+__global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const int* __restrict__ ycur,
+                                           const void* __restrict__ xcur, int phint, int bpp, const float* P,
+                                           const uint16_t* w1bf, const uint16_t* __restrict__ pooled,
+                                           const uint8_t* __restrict__ code, Ctrl* __restrict__ ctrl,
+                                           const void* __restrict__ X, const int* __restrict__ labels,
+                                           float* __restrict__ G, long long* __restrict__ hconv,
+                                           int eager, float* Pw, float* Vw, uint16_t* w1bf_out,
+                                           unsigned long long* st, const float* __restrict__ Gr, const XArgs xa,
+                                           void* __restrict__ xnext, long long* __restrict__ xtag, int auxm) {
+  bwd_body<U8, ONE, CfgGeneric>(hacc, ycur, xcur, phint, bpp, P, w1bf, pooled, code, ctrl, X, labels, G, hconv, eager,
+                                Pw, Vw, w1bf_out, st, Gr, xa, xnext, xtag, auxm);
+}
+
+// The flagship configuration (CfgFlagBwd, single chunk): no packed sizes, no exchange
+// arguments; the aux split follows from the constant grid.  The preloaded dwords are the
+// same pointers as above and the parity hint.
+template <bool U8>
+__global__ __launch_bounds__(512) void bwd_flag(long long* __restrict__ hacc, const int* __restrict__ ycur,
+                                                const void* __restrict__ xcur, const float* P, const uint16_t* w1bf,
+                                                const uint16_t* __restrict__ pooled,
+                                                const uint8_t* __restrict__ code, int phint,
+                                                const float* __restrict__ Gr, Ctrl* __restrict__ ctrl,
+                                                const void* __restrict__ X, const int* __restrict__ labels,
+                                                float* __restrict__ G, long long* __restrict__ hconv, float* Pw,
+                                                float* Vw, uint16_t* w1bf_out, unsigned long long* st,
+                                                void* __restrict__ xnext, long long* __restrict__ xtag) {
+  bwd_body<U8, true, CfgFlagBwd>(hacc, ycur, xcur, phint, 0, P, w1bf, pooled, code, ctrl, X, labels, G, hconv, 1, Pw,
+                                 Vw, w1bf_out, st, Gr, XArgs{}, xnext, xtag, 0);
 }
 
 // =================================================================================
@@ -1278,20 +1423,37 @@ static XArgs xargs(const ConvNetBuffers& b) {
   return a;  // world 0: not sharded
 }
 
+static int ppb_of(const ConvNetBuffers& b, int PP) { return b.ppb > 0 ? b.ppb : PP; }
+
+// The constant-configuration kernels (fwd_flag / bwd_flag) run the step exactly when BOTH
+// launches have the flagship configuration: world 1 (no exchange, no folded all-reduce
+// staging), 64 images, the default slicing of either kernel, eager W1 update -- and the
+// switch is on.  Anything else runs the generic kernels.
+bool convnet2_specialised(const ConvNetBuffers& b, int B, int PP) {
+  using namespace convnet;
+  using namespace convnet2;
+  return !b.force_generic && !b.xa && !b.Gr && !b.hconv_r && B == CH && PP == CfgFlagFwd::PP &&
+         convnet_f1_lg(B) == CfgFlagFwd::LG && ppb_of(b, PP) == CfgFlagBwd::PP && eager2(b, B) == 1;
+}
+
 template <bool U8>
 static void launch2_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) {
   using namespace convnet;
   const int NS = convnet_num_slices(PP);
   const int lg = convnet_f1_lg(B);
   const dim3 g1(NS, (B + (1 << lg) - 1) >> lg);
+  if (convnet2_specialised(b, B, PP)) {
+    hipLaunchKernelGGL((convnet2::fwd_flag<U8>), g1, dim3(512), convnet2_fwd_lds(PP, lg), st, b.xnext, b.xtag, b.w1bf,
+                       b.P, b.V, b.calt, b.hconv, b.G, b.ctrl, b.X, b.pooled, b.code, b.hacc, b.hconv, b.stamps,
+                       b.labels, b.xcur, b.ycur, b.par_hint);
+    return;
+  }
   hipLaunchKernelGGL((convnet2::fwd<U8>), g1, dim3(512), convnet2_fwd_lds(PP, lg), st,
                      B <= CH ? b.xnext : nullptr, b.w1bf, b.P, b.V, b.calt, b.hconv_r ? b.hconv_r : b.hconv,
                      b.Gr ? b.Gr : b.G, B | (PP << 16), lg | (eager2(b, B) << 8), b.ctrl, b.X, b.W1alt, b.V1alt,
                      b.pooled, b.code, b.hacc, b.hconv, b.stamps, xargs(b), b.xtag, b.labels,
                      B <= CH ? b.xcur : nullptr, b.ycur, b.par_hint);
 }
-
-static int ppb_of(const ConvNetBuffers& b, int PP) { return b.ppb > 0 ? b.ppb : PP; }
 
 template <bool U8>
 static void launch2_bwd(const ConvNetBuffers& b, int B, int PPf, hipStream_t st) {
@@ -1300,11 +1462,12 @@ static void launch2_bwd(const ConvNetBuffers& b, int B, int PPf, hipStream_t st)
   const int NS = convnet_num_slices(PP);
   // aux elements (b1/W2/b2 gradients + metric tail) per block, and a power-of-two thread
   // count per element (<= 64) that fits them in 512 threads
-  const int chunk_aux = (convnet2::NAUX2 + NS - 1) / NS;
-  int ltpe = 0;
-  while (ltpe < 6 && (2 << ltpe) * chunk_aux <= 512) ++ltpe;
-  const int auxm = chunk_aux | (ltpe << 16);
-  if (B <= CH)
+  const int auxm = convnet2::aux_split(NS);
+  if (convnet2_specialised(b, B, PPf))
+    hipLaunchKernelGGL((convnet2::bwd_flag<U8>), dim3(NS), dim3(512), convnet2_bwd_lds(PP), st, b.hacc, b.ycur, b.xcur,
+                       b.P, b.w1bf, b.pooled, b.code, b.par_hint, b.G, b.ctrl, b.X, b.labels, b.G, b.hconv, b.P, b.V,
+                       b.w1bf, b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.xnext, b.xtag);
+  else if (B <= CH)
     hipLaunchKernelGGL((convnet2::bwd<U8, true>), dim3(NS), dim3(512), convnet2_bwd_lds(PP), st, b.hacc,
                        B <= CH ? b.ycur : nullptr, B <= CH ? b.xcur : nullptr, b.par_hint, B | (PP << 16), b.P,
                        b.w1bf, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, b.w1bf,
@@ -1355,9 +1518,11 @@ hipError_t convnet2_launch_flush(const ConvNetBuffers& b, int B, hipStream_t st)
 }
 
 hipError_t convnet2_set_lds_limits() {
-  const void* fns[6] = {(const void*)convnet2::fwd<false>,        (const void*)convnet2::fwd<true>,
-                        (const void*)convnet2::bwd<false, true>,  (const void*)convnet2::bwd<true, true>,
-                        (const void*)convnet2::bwd<false, false>, (const void*)convnet2::bwd<true, false>};
+  const void* fns[10] = {(const void*)convnet2::fwd<false>,        (const void*)convnet2::fwd<true>,
+                         (const void*)convnet2::bwd<false, true>,  (const void*)convnet2::bwd<true, true>,
+                         (const void*)convnet2::bwd<false, false>, (const void*)convnet2::bwd<true, false>,
+                         (const void*)convnet2::fwd_flag<false>,   (const void*)convnet2::fwd_flag<true>,
+                         (const void*)convnet2::bwd_flag<false>,   (const void*)convnet2::bwd_flag<true>};
   for (const void* f : fns) {
     hipFuncAttributes at;
     hipError_t e = hipFuncGetAttributes(&at, f);

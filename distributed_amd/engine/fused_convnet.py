@@ -174,6 +174,10 @@ class FusedConvNetEngine(Engine):
         # for the slice's masters)
         self.eager_w1 = self.world == 1 and not force_ar and B <= 64 and env.get_bool("DAMD_EAGER_W1", True)
         bufs["eager_w1"] = int(self.eager_w1)
+        # the flagship configuration (world 1, 64 images, default slicing, eager update) has
+        # step kernels compiled for exactly its sizes; DAMD_SPECIALISED=0 runs the generic
+        # (runtime-size) kernels there too -- same results bit for bit, for A/B runs
+        bufs["specialised"] = int(env.get_bool("DAMD_SPECIALISED", True))
         self.stamps = None
         if env.get_bool("DAMD_STAMPS", False):  # diagnostics: per-phase s_memrealtime stamps
             self.stamps = torch.zeros(3, 256, 16, dtype=torch.int64, device=dev)
@@ -337,6 +341,12 @@ class FusedConvNetEngine(Engine):
         self.steps_done = 0
         self._fault_done = bool(exclude)  # the fault injection fires once per gang
         dlog.debug("fused ConvNet engine: B=%d, slices=%d, graph=%s", B, NS, self.use_graph)
+
+    @property
+    def step_kernels(self) -> str:
+        """"specialised" when a step runs the constant-size kernels of the flagship
+        configuration, else "generic" (csrc/kernels/convnet_step2.hip)."""
+        return self.trainer.step_kernels
 
     # --- host <-> ctrl ---------------------------------------------------------------
     def _ctrl_host(self, soft=False):
