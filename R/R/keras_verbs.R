@@ -17,8 +17,14 @@ dataset_mnist <- function(path = "mnist.npz") .r()$dataset_mnist(path)
 #' @export
 array_reshape <- function(x, dim, order = c("C", "F")) reticulate::array_reshape(x, dim, order = match.arg(order))
 
+#' Class ids -> one-hot rows (targets of loss = 'categorical_crossentropy')
 #' @export
-keras_model_sequential <- function(layers = NULL, name = NULL) .tag(.r()$keras_model_sequential(layers, name))
+to_categorical <- function(y, num_classes = NULL, dtype = "float32") {
+  .r()$to_categorical(y, num_classes = .int(num_classes), dtype = dtype)
+}
+
+#' @export
+keras_model_sequential <-function(layers = NULL, name = NULL) .tag(.r()$keras_model_sequential(layers, name))
 
 #' @export
 layer_conv_2d <- function(object = NULL, filters, kernel_size, strides = c(1L, 1L), padding = "valid",

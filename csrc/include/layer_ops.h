@@ -116,6 +116,8 @@ hipError_t avgpool_bwd(const uint16_t* dy, int N, int H, int W, int C, int ph, i
 hipError_t bn_infer_st(const float* rmean, const float* rvar, const float* gamma, const float* beta, float eps, int C,
                        float* st, hipStream_t s);
 hipError_t logits_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s);
+// logits_store with a row softmax (models whose output is a probability)
+hipError_t softmax_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s);
 hipError_t step_fold(Ctrl* ctrl, float* tail, hipStream_t s);
 // out = a + b (bf16)
 hipError_t add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, long n, hipStream_t s);
@@ -143,6 +145,15 @@ hipError_t colsum(const void* x, int x_f32, int M, int N, int ld, float* out, fl
 hipError_t softmax_xent(const float* logits, int ld, const int32_t* labels, int B, int K, float scale,
                         const Ctrl* ctrl, uint16_t* dlogits, float* tail, float* rows, hipStream_t s,
                         float* bias_grad = nullptr);
+// The same against dense fp32 target rows [.][K] (one-hot or soft; label_smoothing eps in
+// [0, 1): y' = y (1 - eps) + eps / K): loss = -sum y' log softmax, dlogits = (softmax *
+// sum y' - y') * scale, correct = argmax logits == argmax y (first max wins on both).
+// ctrl != nullptr: block b reads target row cursor * global_batch + row0 + b (modulo
+// nsamples in wrap mode) of the epoch-ordered targets and labels[b] < 0 masks the row;
+// ctrl == nullptr: target row b, labels optional.  tail / rows / bias_grad as softmax_xent.
+hipError_t softmax_xent_dense(const float* logits, int ld, const int32_t* labels, const float* targets, int B, int K,
+                              float label_smoothing, float scale, const Ctrl* ctrl, uint16_t* dlogits, float* tail,
+                              float* rows, hipStream_t s, float* bias_grad = nullptr);
 int colsum_splits(int M, int N);
 
 // Optimizer ---------------------------------------------------------------------------------

@@ -1460,93 +1460,30 @@ constexpr int SX_KPT = 4, SX_NW = NT / 64, SX_BK = 1024;
 __device__ __forceinline__ void sx_better(float& v, int& i, float ov, int oi) {
   if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }  // max, ties -> smallest index
 }
+__device__ __forceinline__ void sx_better_sel(float& v, int& i, float ov, int oi) {
+  const bool take = (ov > v) | ((ov == v) & (oi < i));  // sx_better as selects: no branch
+  v = take ? ov : v;
+  i = take ? oi : i;
+}
 __device__ __forceinline__ float sx_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ logits, int ld,
-                                                     const int32_t* __restrict__ labels, int K, float scale,
-                                                     const Ctrl* __restrict__ ctrl, uint16_t* __restrict__ dl,
-                                                     float* tail, float* rows, float* bias_grad) {
-  __shared__ float wmax[SX_NW], wsum[SX_NW], wtail[3][SX_NW];
-  __shared__ int widx[SX_NW];
+// The end of both loss kernels: the batch sums and the logits layer's bias gradient.
+// Every thread of every block calls it (last_arriver holds barriers).
+__device__ __forceinline__ void sx_tail(float row_loss, float row_corr, float row_valid, int K, int ld,
+                                        const uint16_t* dl, float* tail, float* rows, float* bias_grad) {
+  __shared__ float wtail[3][SX_NW];
   __shared__ int last;
   const int b = blockIdx.x, t = threadIdx.x, B = gridDim.x, lane = t & 63, w = t >> 6;
-  const int y = labels[b];
-  float row_loss = 0.f, row_corr = 0.f;
-  if (y < 0) {
-    for (int k = t; k < K; k += NT) dl[(size_t)b * ld + k] = 0;
-  } else {
-    if (ctrl) {
-      const int gb = ctrl->global_batch;
-      const int left = ctrl->nsamples - ctrl->cursor * gb;
-      scale = 1.f / (float)(ctrl->wrap > 0 ? gb : max(1, min(gb, left)));
-    }
-    const float* z = logits + (size_t)b * ld;
-    const bool reg = K <= SX_KPT * NT;  // the row fits the registers
-    float zr[SX_KPT];
-    float mx = -INFINITY;
-    int mi = 0x7fffffff;
-    if (reg) {
-#pragma unroll
-      for (int i = 0; i < SX_KPT; ++i) zr[i] = t + i * NT < K ? z[t + i * NT] : -INFINITY;
-#pragma unroll
-      for (int i = 0; i < SX_KPT; ++i)
-        if (t + i * NT < K && zr[i] > mx) { mx = zr[i]; mi = t + i * NT; }
-    } else {
-      for (int k = t; k < K; k += NT) {
-        const float v = z[k];
-        if (v > mx) { mx = v; mi = k; }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sx_better(mx, mi, __shfl_xor(mx, o), __shfl_xor(mi, o));
-    if (lane == 0) { wmax[w] = mx; widx[w] = mi; }
-    __syncthreads();
-    float zmax = wmax[0];
-    int amax = widx[0];
-#pragma unroll
-    for (int v = 1; v < SX_NW; ++v) sx_better(zmax, amax, wmax[v], widx[v]);
-    float se = 0.f;
-    if (reg) {
-#pragma unroll
-      for (int i = 0; i < SX_KPT; ++i) {
-        zr[i] = t + i * NT < K ? __expf(zr[i] - zmax) : 0.f;
-        se += zr[i];
-      }
-    } else {
-      for (int k = t; k < K; k += NT) se += __expf(z[k] - zmax);
-    }
-    se = sx_wave_sum(se);
-    if (lane == 0) wsum[w] = se;
-    __syncthreads();
-    float sum = wsum[0];
-#pragma unroll
-    for (int v = 1; v < SX_NW; ++v) sum += wsum[v];
-    const float inv = 1.f / sum;
-    if (reg) {
-#pragma unroll
-      for (int i = 0; i < SX_KPT; ++i) {
-        const int k = t + i * NT;
-        if (k < K) dl[(size_t)b * ld + k] = f2bf((zr[i] * inv - (k == y ? 1.f : 0.f)) * scale);
-      }
-    } else {
-      for (int k = t; k < K; k += NT) {
-        const float p = __expf(z[k] - zmax) * inv;
-        dl[(size_t)b * ld + k] = f2bf((p - (k == y ? 1.f : 0.f)) * scale);
-      }
-    }
-    row_loss = logf(sum) + zmax - z[y];
-    row_corr = amax == y ? 1.f : 0.f;
-  }
   // the batch sums in a fixed order (no float atomics: replays and graph / eager runs give
   // the same bits): every row stores (loss, correct, valid), the last block to arrive adds
   // them up (fixed shuffle tree + fixed wave order) and re-arms the arrival counter rows[3 B]
   if (t == 0) {
     rows[3 * b] = row_loss;
     rows[3 * b + 1] = row_corr;
-    rows[3 * b + 2] = y < 0 ? 0.f : 1.f;
+    rows[3 * b + 2] = row_valid;
   }
   int* counter = reinterpret_cast<int*>(rows + 3 * B);
   if (!last_arriver(counter, B, &last)) return;
@@ -1615,6 +1552,208 @@ __global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ l
   }
 }
 
+__global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ logits, int ld,
+                                                     const int32_t* __restrict__ labels, int K, float scale,
+                                                     const Ctrl* __restrict__ ctrl, uint16_t* __restrict__ dl,
+                                                     float* tail, float* rows, float* bias_grad) {
+  __shared__ float wmax[SX_NW], wsum[SX_NW];
+  __shared__ int widx[SX_NW];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int y = labels[b];
+  float row_loss = 0.f, row_corr = 0.f;
+  if (y < 0) {
+    for (int k = t; k < K; k += NT) dl[(size_t)b * ld + k] = 0;
+  } else {
+    if (ctrl) {
+      const int gb = ctrl->global_batch;
+      const int left = ctrl->nsamples - ctrl->cursor * gb;
+      scale = 1.f / (float)(ctrl->wrap > 0 ? gb : max(1, min(gb, left)));
+    }
+    const float* z = logits + (size_t)b * ld;
+    const bool reg = K <= SX_KPT * NT;  // the row fits the registers
+    float zr[SX_KPT];
+    float mx = -INFINITY;
+    int mi = 0x7fffffff;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) zr[i] = t + i * NT < K ? z[t + i * NT] : -INFINITY;
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i)
+        if (t + i * NT < K && zr[i] > mx) { mx = zr[i]; mi = t + i * NT; }
+    } else {
+      for (int k = t; k < K; k += NT) {
+        const float v = z[k];
+        if (v > mx) { mx = v; mi = k; }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sx_better(mx, mi, __shfl_xor(mx, o), __shfl_xor(mi, o));
+    if (lane == 0) { wmax[w] = mx; widx[w] = mi; }
+    __syncthreads();
+    float zmax = wmax[0];
+    int amax = widx[0];
+#pragma unroll
+    for (int v = 1; v < SX_NW; ++v) sx_better(zmax, amax, wmax[v], widx[v]);
+    float se = 0.f;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        zr[i] = t + i * NT < K ? __expf(zr[i] - zmax) : 0.f;
+        se += zr[i];
+      }
+    } else {
+      for (int k = t; k < K; k += NT) se += __expf(z[k] - zmax);
+    }
+    se = sx_wave_sum(se);
+    if (lane == 0) wsum[w] = se;
+    __syncthreads();
+    float sum = wsum[0];
+#pragma unroll
+    for (int v = 1; v < SX_NW; ++v) sum += wsum[v];
+    const float inv = 1.f / sum;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        const int k = t + i * NT;
+        if (k < K) dl[(size_t)b * ld + k] = f2bf((zr[i] * inv - (k == y ? 1.f : 0.f)) * scale);
+      }
+    } else {
+      for (int k = t; k < K; k += NT) {
+        const float p = __expf(z[k] - zmax) * inv;
+        dl[(size_t)b * ld + k] = f2bf((p - (k == y ? 1.f : 0.f)) * scale);
+      }
+    }
+    row_loss = logf(sum) + zmax - z[y];
+    row_corr = amax == y ? 1.f : 0.f;
+  }
+  sx_tail(row_loss, row_corr, y < 0 ? 0.f : 1.f, K, ld, dl, tail, rows, bias_grad);
+}
+
+// Softmax cross-entropy against dense fp32 target rows (one-hot / soft targets) with label
+// smoothing: y' = y (1 - eps) + eps / K, S = sum y', loss = S lse - sum y' z, dlogits =
+// (p S - y') scale (S: targets need not sum to 1), correct = argmax z == argmax y, both
+// ties to the smallest index.  The structure of softmax_xent_k; the targets ride along
+// with the logits (both loads issued together), and the first LDS exchange carries the
+// two argmaxes, S and the dot product at once, so the row costs the same two barriers.
+// With ctrl the block finds its target row as gather_batch_k finds the input row (the
+// epoch-ordered [n][K] targets are read in place), else targets are indexed by the block.
+// labels (optional): labels[b] < 0 marks a row past the end of the data.
+__global__ __launch_bounds__(NT) void softmax_xent_dense_k(const float* __restrict__ logits, int ld,
+                                                           const int32_t* __restrict__ labels,
+                                                           const float* __restrict__ targets, int K, float eps,
+                                                           float scale, const Ctrl* __restrict__ ctrl,
+                                                           uint16_t* __restrict__ dl, float* tail, float* rows,
+                                                           float* bias_grad) {
+  __shared__ float wmax[SX_NW], wymax[SX_NW], wS[SX_NW], wdot[SX_NW], wsum[SX_NW];
+  __shared__ int widx[SX_NW], wyidx[SX_NW];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const bool valid = labels == nullptr || labels[b] >= 0;
+  float row_loss = 0.f, row_corr = 0.f;
+  if (!valid) {
+    for (int k = t; k < K; k += NT) dl[(size_t)b * ld + k] = 0;
+  } else {
+    long row = b;
+    if (ctrl) {
+      const int gb = ctrl->global_batch;
+      const int left = ctrl->nsamples - ctrl->cursor * gb;
+      scale = 1.f / (float)(ctrl->wrap > 0 ? gb : max(1, min(gb, left)));
+      const long base = (long)ctrl->cursor * gb + ctrl->row0;
+      row = ctrl->wrap > 0 ? (base + b) % ctrl->nsamples : base + b;
+    }
+    const float* z = logits + (size_t)b * ld;
+    const float* yt = targets + (size_t)row * K;
+    const float keep = 1.f - eps, uni = eps / (float)K;
+    const bool reg = K <= SX_KPT * NT;  // the row fits the registers
+    float zr[SX_KPT], yr[SX_KPT];
+    float mx = -INFINITY, my = -INFINITY, S = 0.f, dot = 0.f;
+    int mi = 0x7fffffff, yi = 0x7fffffff;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        const bool in = t + i * NT < K;
+        zr[i] = in ? z[t + i * NT] : -INFINITY;
+        yr[i] = in ? yt[t + i * NT] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        if (t + i * NT >= K) continue;
+        if (zr[i] > mx) { mx = zr[i]; mi = t + i * NT; }
+        if (yr[i] > my) { my = yr[i]; yi = t + i * NT; }
+        yr[i] = yr[i] * keep + uni;
+        S += yr[i];
+        dot += yr[i] * zr[i];
+      }
+    } else {
+      for (int k = t; k < K; k += NT) {
+        const float v = z[k], u = yt[k];
+        if (v > mx) { mx = v; mi = k; }
+        if (u > my) { my = u; yi = k; }
+        const float ys = u * keep + uni;
+        S += ys;
+        dot += ys * v;
+      }
+    }
+    // the four reductions level by level: a level's six shuffles go out together and the
+    // argmaxes are selects (sx_better's branches made the compiler run the chains one after
+    // the other, 12 dependent shuffle round trips more than softmax_xent_k: +1.07 us at
+    // 64 x 1000)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(mx, o), oy = __shfl_xor(my, o), oS = __shfl_xor(S, o), od = __shfl_xor(dot, o);
+      const int oi = __shfl_xor(mi, o), oyi = __shfl_xor(yi, o);
+      sx_better_sel(mx, mi, ov, oi);
+      sx_better_sel(my, yi, oy, oyi);
+      S += oS;
+      dot += od;
+    }
+    if (lane == 0) { wmax[w] = mx; widx[w] = mi; wymax[w] = my; wyidx[w] = yi; wS[w] = S; wdot[w] = dot; }
+    __syncthreads();
+    float zmax = wmax[0], ymax = wymax[0];
+    int amax = widx[0], ymaxi = wyidx[0];
+    S = wS[0];
+    dot = wdot[0];
+#pragma unroll
+    for (int v = 1; v < SX_NW; ++v) {
+      sx_better_sel(zmax, amax, wmax[v], widx[v]);
+      sx_better_sel(ymax, ymaxi, wymax[v], wyidx[v]);
+      S += wS[v];
+      dot += wdot[v];
+    }
+    float se = 0.f;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        zr[i] = t + i * NT < K ? __expf(zr[i] - zmax) : 0.f;
+        se += zr[i];
+      }
+    } else {
+      for (int k = t; k < K; k += NT) se += __expf(z[k] - zmax);
+    }
+    se = sx_wave_sum(se);
+    if (lane == 0) wsum[w] = se;
+    __syncthreads();
+    float sum = wsum[0];
+#pragma unroll
+    for (int v = 1; v < SX_NW; ++v) sum += wsum[v];
+    const float inv = 1.f / sum;
+    if (reg) {
+#pragma unroll
+      for (int i = 0; i < SX_KPT; ++i) {
+        const int k = t + i * NT;
+        if (k < K) dl[(size_t)b * ld + k] = f2bf((zr[i] * inv * S - yr[i]) * scale);
+      }
+    } else {
+      for (int k = t; k < K; k += NT) {
+        const float p = __expf(z[k] - zmax) * inv;
+        dl[(size_t)b * ld + k] = f2bf((p * S - (yt[k] * keep + uni)) * scale);
+      }
+    }
+    row_loss = S * (logf(sum) + zmax) - dot;
+    row_corr = amax == ymaxi ? 1.f : 0.f;
+  }
+  sx_tail(row_loss, row_corr, valid ? 1.f : 0.f, K, ld, dl, tail, rows, bias_grad);
+}
+
 // ---- inference (predict / evaluate through the native forward plan) ----------------------
 // BatchNorm with the moving statistics: the same st rows bn_finalize writes from batch
 // statistics (mean, 1/sqrt(var + eps), scale, shift), so every BN apply / fused residual /
@@ -1641,6 +1780,62 @@ __global__ __launch_bounds__(NT) void logits_store_k(const float* __restrict__ l
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < (long)B * K; i += (long)gridDim.x * NT) {
     const int r = (int)(i / K), k = (int)(i % K);
     if (base + r < n) out[(base + r) * K + k] = logits[(long)r * ld + k];
+  }
+}
+
+// logits_store_k for a model whose output is a softmax: out[global row][K] = softmax of the
+// step's logits row.  One block per row (the row held in registers up to SX_KPT * NT
+// columns, re-read beyond), rows past the end of the data dropped.
+__global__ __launch_bounds__(NT) void softmax_store_k(const float* __restrict__ logits, int ld, int K,
+                                                      const Ctrl* __restrict__ ctrl, float* __restrict__ out) {
+  __shared__ float wmax[SX_NW], wsum[SX_NW];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const long r = (long)ctrl->cursor * ctrl->global_batch + ctrl->row0 + b;
+  if (r >= ctrl->nsamples) return;  // the whole block: no barrier is left waiting
+  const float* z = logits + (size_t)b * ld;
+  float* o = out + r * K;
+  const bool reg = K <= SX_KPT * NT;
+  float zr[SX_KPT];
+  float mx = -INFINITY;
+  if (reg) {
+#pragma unroll
+    for (int i = 0; i < SX_KPT; ++i) {
+      zr[i] = t + i * NT < K ? z[t + i * NT] : -INFINITY;
+      mx = fmaxf(mx, zr[i]);
+    }
+  } else {
+    for (int k = t; k < K; k += NT) mx = fmaxf(mx, z[k]);
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+  if (lane == 0) wmax[w] = mx;
+  __syncthreads();
+  float zmax = wmax[0];
+#pragma unroll
+  for (int v = 1; v < SX_NW; ++v) zmax = fmaxf(zmax, wmax[v]);
+  float se = 0.f;
+  if (reg) {
+#pragma unroll
+    for (int i = 0; i < SX_KPT; ++i) {
+      zr[i] = t + i * NT < K ? __expf(zr[i] - zmax) : 0.f;
+      se += zr[i];
+    }
+  } else {
+    for (int k = t; k < K; k += NT) se += __expf(z[k] - zmax);
+  }
+  se = sx_wave_sum(se);
+  if (lane == 0) wsum[w] = se;
+  __syncthreads();
+  float sum = wsum[0];
+#pragma unroll
+  for (int v = 1; v < SX_NW; ++v) sum += wsum[v];
+  const float inv = 1.f / sum;
+  if (reg) {
+#pragma unroll
+    for (int i = 0; i < SX_KPT; ++i)
+      if (t + i * NT < K) o[t + i * NT] = zr[i] * inv;
+  } else {
+    for (int k = t; k < K; k += NT) o[k] = __expf(z[k] - zmax) * inv;
   }
 }
 
@@ -1921,6 +2116,12 @@ hipError_t bn_infer_st(const float* rmean, const float* rvar, const float* gamma
 hipError_t logits_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s) {
   if (K > ld) return hipErrorInvalidValue;
   hipLaunchKernelGGL(logits_store_k, dim3(grid_for((long)B * K)), dim3(NT), 0, s, logits, ld, K, B, ctrl, out);
+  return hipGetLastError();
+}
+
+hipError_t softmax_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s) {
+  if (K > ld || K < 1 || B < 1 || !ctrl) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(softmax_store_k, dim3(B), dim3(NT), 0, s, logits, ld, K, ctrl, out);
   return hipGetLastError();
 }
 
@@ -2295,6 +2496,18 @@ hipError_t softmax_xent(const float* logits, int ld, const int32_t* labels, int 
   if (bias_grad && colsum_splits(B, K) != 1) return hipErrorInvalidValue;  // the fold keeps colsum's order
   hipLaunchKernelGGL(softmax_xent_k, dim3(B), dim3(NT), 0, s, logits, ld, labels, K, scale, ctrl, dlogits, tail, rows,
                      bias_grad);
+  return hipGetLastError();
+}
+
+hipError_t softmax_xent_dense(const float* logits, int ld, const int32_t* labels, const float* targets, int B, int K,
+                              float label_smoothing, float scale, const Ctrl* ctrl, uint16_t* dlogits, float* tail,
+                              float* rows, hipStream_t s, float* bias_grad) {
+  if (!rows || !targets || B < 1 || K < 1 || K > ld) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return hipErrorInvalidValue;
+  if (ctrl && !labels) return hipErrorInvalidValue;  // the step's row validity comes from gather_batch
+  if (bias_grad && colsum_splits(B, K) != 1) return hipErrorInvalidValue;  // the fold keeps colsum's order
+  hipLaunchKernelGGL(softmax_xent_dense_k, dim3(B), dim3(NT), 0, s, logits, ld, labels, targets, K, label_smoothing,
+                     scale, ctrl, dlogits, tail, rows, bias_grad);
   return hipGetLastError();
 }
 

@@ -339,6 +339,20 @@ void register_kernel_ops(py::module_& m) {
           "softmax_xent");
   }, py::arg("logits"), py::arg("ld"), py::arg("labels"), py::arg("B"), py::arg("K"), py::arg("scale"),
      py::arg("ctrl"), py::arg("dl"), py::arg("tail"), py::arg("rows"), py::arg("s"), py::arg("bias_grad") = 0);
+  m.def("softmax_xent_dense", [](U logits, int ld, U labels, U targets, int B, int K, float label_smoothing,
+                                 float scale, U ctrl, U dl, U tail, U rows, U s, U bias_grad) {
+    check(damd::softmax_xent_dense(P_<const float>(logits), ld, P_<const int32_t>(labels), P_<const float>(targets), B,
+                                   K, label_smoothing, scale, P_<const damd::Ctrl>(ctrl), P_<u16>(dl),
+                                   P_<float>(tail), P_<float>(rows), P_<ihipStream_t>(s), P_<float>(bias_grad)),
+          "softmax_xent_dense");
+  }, py::arg("logits"), py::arg("ld"), py::arg("labels"), py::arg("targets"), py::arg("B"), py::arg("K"),
+     py::arg("label_smoothing"), py::arg("scale"), py::arg("ctrl"), py::arg("dl"), py::arg("tail"), py::arg("rows"),
+     py::arg("s"), py::arg("bias_grad") = 0);
+  m.def("softmax_store", [](U logits, int ld, int K, int B, U ctrl, U out, U s) {
+    check(damd::softmax_store(P_<const float>(logits), ld, K, B, P_<const damd::Ctrl>(ctrl), P_<float>(out),
+                              P_<ihipStream_t>(s)),
+          "softmax_store");
+  });
   m.def("sgd_step", [](U P, U G, U V, U Pb, long n, U ctrl, U tail, U s) {
     check(damd::sgd_step(P_<float>(P), P_<const float>(G), P_<float>(V), P_<u16>(Pb), n, P_<damd::Ctrl>(ctrl),
                          P_<const float>(tail), P_<ihipStream_t>(s)),

@@ -109,6 +109,78 @@ def _act_name(layer) -> str:
     return getattr(act, "__name__", "linear") if act is not None else "linear"
 
 
+def _is_softmax(layer) -> bool:
+    k = type(layer).__name__
+    return k == "Softmax" or (k == "Activation" and _act_name(layer) == "softmax")
+
+
+def output_head(seq):
+    """The output head of a layer graph (``_layer_graph``'s ``seq``): (kind, Dense layer,
+    terminal softmax layer or None, reason).  kind is
+
+    * ``'logits'``: the model ends in a linear Dense;
+    * ``'probs'``: the last Dense has ``activation='softmax'``, or a linear Dense is followed
+      by a terminal ``Softmax()`` / ``Activation('softmax')``;
+    * None (with the reason) for anything else.
+
+    Either way the native plan produces the fp32 logits of that Dense: a terminal softmax
+    lives in the loss kernel (training, evaluate) or the ``softmax_store`` tail (predict)."""
+    last, ins, _ = seq[-1]
+    if _is_softmax(last):
+        prod = [e[0] for e in seq if e[2] == ins[0]] if len(ins) == 1 else []
+        users = [e for e in seq if ins[0] in e[1]] if len(ins) == 1 else []
+        if (len(prod) == 1 and len(users) == 1 and type(prod[0]).__name__ == "Dense"
+                and _act_name(prod[0]) == "linear"):
+            return "probs", prod[0], last, ""
+        return None, None, None, "a terminal softmax must follow a linear Dense"
+    if type(last).__name__ == "Dense" and _act_name(last) == "linear":
+        return "logits", last, None, ""
+    if type(last).__name__ == "Dense" and _act_name(last) == "softmax":
+        return "probs", last, None, ""
+    return None, None, None, "the model must end in a linear Dense (logits) or a softmax over one"
+
+
+def loss_head_ok(model, head_kind):
+    """(ok, reason): the compiled loss and metrics are ones the device loss head computes for
+    a model whose output is ``head_kind`` ('logits' / 'probs').
+
+    Sparse and categorical cross-entropy (label smoothing in [0, 1)) with ``from_logits``
+    matching the head; metrics by class: SparseCategoricalAccuracy with the sparse loss,
+    CategoricalAccuracy with the categorical one (what 'accuracy' / 'acc' resolve to).
+
+    For a 'probs' head the loss and its gradient are computed from the logits, as tf.keras
+    does for softmax-terminated models.  That equals the PyTorch path's ``per_sample`` on
+    the probabilities except where a probability leaves [1e-7, 1 - 1e-7], which that path
+    clips and this one does not."""
+    from ..keras import losses, metrics
+
+    loss = model.loss
+    if isinstance(loss, losses.SparseCategoricalCrossentropy):
+        want = metrics.SparseCategoricalAccuracy
+    elif isinstance(loss, losses.CategoricalCrossentropy):
+        want = metrics.CategoricalAccuracy
+        eps = float(loss.label_smoothing or 0.0)
+        if not 0.0 <= eps < 1.0:
+            return False, f"label_smoothing {eps} outside [0, 1)"
+    else:
+        return False, "loss"
+    if head_kind == "probs" and loss.from_logits:
+        return False, "from_logits=True on a softmax output would apply softmax twice"
+    if head_kind == "logits" and not loss.from_logits:
+        return False, "from_logits=False on a linear (logits) output"
+    for m in model.compiled_metrics:
+        if not isinstance(m, want):
+            return False, f"metric {m.name} ({type(m).__name__}) with {type(loss).__name__}"
+    return True, ""
+
+
+def dense_targets(model) -> bool:
+    """The compiled loss takes dense [n, K] target rows (one-hot / soft), not class ids."""
+    from ..keras import losses
+
+    return isinstance(model.loss, losses.CategoricalCrossentropy)
+
+
 def _param_weights(model):
     """Every layer weight the forward plan reads (kernels, biases, BN gamma / beta),
     trainable or frozen -- i.e. all weights except the BN moving statistics."""
@@ -154,35 +226,41 @@ class NativeGraphEngine(Engine):
             return False, "not on a GPU"
         if type(model.optimizer) not in (optimizers.SGD, optimizers.Adam, optimizers.RMSprop):
             return False, f"optimizer {type(model.optimizer).__name__}"
-        if not (isinstance(model.loss, losses.SparseCategoricalCrossentropy) and model.loss.from_logits):
+        if not isinstance(model.loss, (losses.SparseCategoricalCrossentropy, losses.CategoricalCrossentropy)):
             return False, "loss"
-        for m in model.compiled_metrics:
-            if m.name not in ("accuracy", "acc", "sparse_categorical_accuracy"):
-                return False, f"metric {m.name}"
         # the training plan keeps one flat buffer of trainable weights: a frozen kernel /
         # bias / gamma / beta (layer.trainable = False) trains on the generic path
         trainable = {id(w) for w in model.trainable_weights}
         if any(id(w) not in trainable for w in _param_weights(model)):
             return False, "frozen layer weights"
-        return NativeGraphEngine.layers_eligible(model)
+        ok, why = NativeGraphEngine.layers_eligible(model)
+        if not ok:
+            return ok, why
+        return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
 
     @staticmethod
     def layers_eligible(model):
         """(ok, reason): every layer of ``model`` has a native forward + backward kernel
-        and the model ends in a linear Dense (the logits)."""
+        and the model ends in one of the heads of :func:`output_head` (a linear Dense, a
+        softmax Dense, or a linear Dense under a terminal softmax layer).  A softmax
+        anywhere else has no kernel."""
         try:
             seq, _, out_key, in_shape = _layer_graph(model)
         except Exception as e:  # pragma: no cover
             return False, f"graph: {e}"
         if len(in_shape) != 3:
             return False, "input must be an image (H, W, C)"
+        head_kind, head_dense, head_softmax, head_why = output_head(seq)
         for l, ins, _ in seq:
             k = type(l).__name__
+            if l is head_softmax:
+                continue  # planned away: the loss / predict tail applies it
             if k not in NativeGraphEngine.SUPPORTED:
                 return False, f"layer {k}"
             act = getattr(l, "activation", None)
             an = getattr(act, "__name__", "linear") if act is not None else "linear"
-            if k in ("Conv2D", "Dense", "Activation") and an not in NativeGraphEngine.ACTIVATIONS:
+            if (k in ("Conv2D", "Dense", "Activation") and an not in NativeGraphEngine.ACTIVATIONS
+                    and l is not head_dense):
                 return False, f"activation {an}"
             if k == "ReLU" and (l.max_value is not None or l.negative_slope or l.threshold):
                 return False, "ReLU options"
@@ -199,11 +277,10 @@ class NativeGraphEngine(Engine):
                 return False, "BN axis"
             if k == "Add" and len(ins) != 2:
                 return False, "Add arity"
-            if k == "Dense" and l is not seq[-1][0] and l.units % 8:
+            if k == "Dense" and l is not seq[-1][0] and l is not head_dense and l.units % 8:
                 return False, "hidden Dense units must be a multiple of 8"
-        last = seq[-1][0]
-        if type(last).__name__ != "Dense" or getattr(last.activation, "__name__", "") != "linear":
-            return False, "the model must end in a linear Dense (logits)"
+        if head_kind is None:
+            return False, head_why
         return True, ""
 
     # ------------------------------------------------------------------------------------
@@ -268,6 +345,10 @@ class NativeGraphEngine(Engine):
         self.graph = None
         self._phase_events = None  # phase_times(): (name, event) marks of an eager step
         self.feed = None
+        # target kind of the loss launch: class ids (softmax_xent) or dense [n, K] rows
+        # (softmax_xent_dense, with the loss' label smoothing)
+        self.dense_y = dense_targets(model)
+        self.label_smoothing = float(getattr(model.loss, "label_smoothing", 0.0) or 0.0) if self.dense_y else 0.0
         self._plan()
         self._plan_buckets(env.get_float("DAMD_BUCKET_MB", 8.0), env.get_float("DAMD_BUCKET_LAST_MB", 1.0))
         # bucket transport at world > 1 (DAMD_ALLREDUCE): RCCL (auto, when the RCCL
@@ -411,6 +492,16 @@ class NativeGraphEngine(Engine):
             nodes.append(nd)
         self.logits_t = tensors[out_key]
         self.nodes = nodes
+        # the output head: the Dense whose fp32 logits feed the loss; a terminal softmax
+        # layer is planned away (dead, aliasing the logits)
+        self.head_kind, head_dense, head_softmax, _ = output_head(seq)
+        self.head_node = next((nd for nd in nodes if nd.layer is head_dense), None)
+        if self.head_node is not None:
+            self.head_node.attrs["logits"] = True
+        if head_softmax is not None:
+            sm = next(nd for nd in nodes if nd.layer is head_softmax)
+            sm.attrs["dead"] = True
+            self._alias(sm.out, sm.inputs[0])
         # packed-tap stem: a <= 4-channel input read only by stride-2 convs of <= 8 columns
         # is stored with 4 channels and those convs run K = KH x 32 (ops/hip.py stem4_ok)
         if c <= 4 and x0.consumers and env.get_bool("DAMD_STEM4", True) and all(
@@ -534,7 +625,9 @@ class NativeGraphEngine(Engine):
 
         alloc(self.x0)
         self.labels = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        last = self.nodes[-1]
+        last = self.head_node
+        if last is None:
+            raise ValueError("native plan: " + output_head(_layer_graph(self.model)[0])[3])
         for nd in self.nodes:
             if nd is last or nd.attrs.get("pool") is not None:  # stem-fused BN: no output tensor
                 continue
@@ -545,7 +638,6 @@ class NativeGraphEngine(Engine):
         self.logits = torch.zeros(self.B, self.Kp, dtype=torch.float32, device=dev)
         self.dlogits = torch.zeros(self.B, self.Kp, dtype=torch.bfloat16, device=dev)
         self.xent_rows = H.xent_rows(self.B, dev)  # fixed-order loss / metric sums
-        last.attrs["logits"] = True
         # per-node scratch
         self.st_ident = torch.cat([torch.zeros(1, 1), torch.ones(1, 1), torch.ones(1, 1), torch.zeros(1, 1)])
         self._ident_cache = {}
@@ -602,7 +694,7 @@ class NativeGraphEngine(Engine):
                     nd.attrs["dw_pad"] = torch.zeros(kin, up, dtype=torch.float32, device=dev)
                     if l.use_bias:
                         nd.attrs["b_pad"] = torch.zeros(up, dtype=torch.float32, device=dev)
-                if _act_name(l) != "linear":
+                if _act_name(l) != "linear" and not nd.attrs.get("logits"):  # (a softmax head: in the loss)
                     nd.attrs["dz"] = torch.zeros(nd.out.shape, dtype=torch.bfloat16, device=dev)
         self._plan_bn_fin()
         self._plan_bn_dgrad_fusion()
@@ -913,13 +1005,23 @@ class NativeGraphEngine(Engine):
         h, w, c = self.in_shape
         if tuple(x.shape[1:]) not in ((h, w, c),) and not (c == 1 and tuple(x.shape[1:]) == (h, w)):
             raise ValueError(f"native graph engine expects inputs of shape {(h, w, c)}, got {x.shape[1:]}")
+        if self.dense_y:
+            ys = np.shape(y)
+            if len(ys) != 2 or ys[1] != self.K:
+                raise ValueError(f"{type(self.model.loss).__name__} takes one-hot / dense targets of shape "
+                                 f"(n, {self.K}) for this model, got y of shape {tuple(ys)}"
+                                 " (to_categorical(y), or the sparse loss for class ids)")
         key = (id(x), id(y), len(x))
         if self.feed is None or getattr(self, "_feed_key", None) != key:
             torch.cuda.synchronize(self.device)
             self.feed = DataFeed(x, y, self.device, flatten=True, allow_u8=env.get_bool("DAMD_X_U8", True))
+            if self.dense_y and (self.feed.y.dtype != torch.float32 or tuple(self.feed.y.shape) !=
+                                 (self.feed.n, self.K)):
+                raise ValueError(f"dense targets must be (n, {self.K}) numbers, got {tuple(self.feed.y.shape)}")
             self._feed_key = key
             self.x_ep = torch.empty_like(self.feed.x)
             self.y_ep = torch.empty_like(self.feed.y)
+            self.y_zero = torch.zeros(self.feed.n, dtype=torch.int32, device=self.device) if self.dense_y else None
             self.graph = None  # data pointers changed
             self._ctrl_write({C_NS: self.feed.n})
         return self.feed
@@ -957,7 +1059,10 @@ class NativeGraphEngine(Engine):
         # between this launch and that conv
         self._pad_folded = next((nd for nd in live if nd.kind == "Conv2D" and self._pad_job(nd) is not None), None)
         job = self._pad_job(self._pad_folded) if self._pad_folded is not None else None
-        C.gather_batch(self.x_ep.data_ptr(), int(self.feed.x_u8), 255.0, self.y_ep.data_ptr(), self.ctrl.data_ptr(),
+        # (dense targets: gather_batch gets an all-zero label array, so self.labels still
+        # carries 0 for a real row and -1 for one past the end of the data)
+        y_ids = self.y_zero if self.dense_y else self.y_ep
+        C.gather_batch(self.x_ep.data_ptr(), int(self.feed.x_u8), 255.0, y_ids.data_ptr(), self.ctrl.data_ptr(),
                        B, h * w, c, self.cin_pad, self.x0.buf.data_ptr(), self.labels.data_ptr(), s,
                        zero=self.G.data_ptr(), zero_bytes=self.G.numel() * 4,
                        zero2=acc.data_ptr() if acc is not None else 0, zero2_bytes=acc.numel() * 8 if acc is not None else 0,
@@ -965,14 +1070,22 @@ class NativeGraphEngine(Engine):
                        pc_dims=list(job[2:]) if job else [])
         for nd in live:
             getattr(self, "_fwd_" + nd.kind)(nd)
-        last = self.nodes[-1]
+        last = self.head_node
         # the logits layer's bias gradient comes out of the loss launch (no colsum launch;
         # DAMD_XENT_BIAS=0: the colsum launch, the same bits)
         fold = (last.kind == "Dense" and last.layer.use_bias and "dz" not in last.attrs
                 and H.softmax_bias_fold_ok(self.B, self.K) and env.get_bool("DAMD_XENT_BIAS", True))
         last.attrs["bias_folded"] = fold
-        H.softmax_xent(self.logits, self.labels, self.K, 1.0 / self.global_batch, self.dlogits, self.G[self.nparam:],
-                       ctrl=self.ctrl, rows=self.xent_rows, bias_grad=self.gviews[id(last.layer.bias)] if fold else None)
+        bias_grad = self.gviews[id(last.layer.bias)] if fold else None
+        if self.dense_y:
+            # one-hot / soft targets: the kernel reads the epoch-ordered [n, K] rows in place
+            # at the device cursor (self.labels: the 0 / -1 row validity gather_batch wrote)
+            H.softmax_xent_dense(self.logits, self.y_ep, self.K, 1.0 / self.global_batch, self.dlogits,
+                                 self.G[self.nparam:], label_smoothing=self.label_smoothing, labels=self.labels,
+                                 ctrl=self.ctrl, rows=self.xent_rows, bias_grad=bias_grad)
+        else:
+            H.softmax_xent(self.logits, self.labels, self.K, 1.0 / self.global_batch, self.dlogits,
+                           self.G[self.nparam:], ctrl=self.ctrl, rows=self.xent_rows, bias_grad=bias_grad)
         self._mark("forward")
         for t in self._all_tensors():
             t.root().written = False

@@ -10,7 +10,9 @@ every epoch).  Here that runs on the same lowered plan as training
 * BatchNorm runs with the MOVING statistics: ``bn_infer_st`` turns them into the same
   (mean, invstd, scale, shift) rows the training plan derives from batch statistics, so
   the fused BN / residual / stem-pool kernels are reused unchanged; Dropout is identity;
-* one step = gather -> forward -> (``logits_store`` | ``softmax_xent``) -> ``step_fold``
+* one step = gather -> forward -> (``logits_store`` or, for a softmax output,
+  ``softmax_store`` | ``softmax_xent`` or, for one-hot / dense targets,
+  ``softmax_xent_dense``) -> ``step_fold``
   (cursor + metric accumulators in the device ``Ctrl`` block), captured once as a HIP
   graph and replayed ceil(n / batch) times: no host synchronisation per batch, one at
   the end of the call.
@@ -28,8 +30,8 @@ import torch
 
 from ..ops import hip as H
 from ..utils import logging as dlog
-from .native_graph import (C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, NativeGraphEngine, _i2f, _pad8,
-                           _param_weights)
+from .native_graph import (C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, NativeGraphEngine, _i2f,
+                           _layer_graph, _pad8, _param_weights, dense_targets, loss_head_ok, output_head)
 
 
 class NativeInference(NativeGraphEngine):
@@ -39,17 +41,12 @@ class NativeInference(NativeGraphEngine):
 
     @staticmethod
     def eligible(model, device, evaluate: bool = False) -> Tuple[bool, str]:
-        from ..keras import losses
-
         if torch.device(device).type != "cuda":
             return False, "not on a GPU"
-        if evaluate:
-            if not (isinstance(model.loss, losses.SparseCategoricalCrossentropy) and model.loss.from_logits):
-                return False, "loss"
-            for m in model.compiled_metrics:
-                if m.name not in ("accuracy", "acc", "sparse_categorical_accuracy"):
-                    return False, f"metric {m.name}"
-        return NativeGraphEngine.layers_eligible(model)
+        ok, why = NativeGraphEngine.layers_eligible(model)
+        if ok and evaluate:  # (predict uses no loss: its eligibility is the layers' alone)
+            return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
+        return ok, why
 
     def __init__(self, model, batch: int, device):
         # no Engine.__init__: an inference plan owns no strategy, gradients or optimizer
@@ -131,17 +128,27 @@ class NativeInference(NativeGraphEngine):
             if not nd.attrs.get("dead"):
                 getattr(self, "_fwd_" + nd.kind)(nd)
         if mode == "predict":
-            C.logits_store(self.logits.data_ptr(), self.Kp, self.K, B, self.ctrl.data_ptr(),
-                           self._bufs["out"].data_ptr(), s)
+            if self.head_kind == "probs":  # the model's output is the softmax of the logits
+                H.softmax_store(self.logits, self.K, self.ctrl, self._bufs["out"])
+            else:
+                C.logits_store(self.logits.data_ptr(), self.Kp, self.K, B, self.ctrl.data_ptr(),
+                               self._bufs["out"].data_ptr(), s)
             C.step_fold(self.ctrl.data_ptr(), 0, s)
+        elif mode == "evaluate_dense":
+            # y: all-zero ids (gather_batch turns them into the 0 / -1 row validity); the
+            # [n, K] target rows are read in place at the device cursor
+            H.softmax_xent_dense(self.logits, self._bufs["yd"], self.K, 1.0 / B, self.dlogits, self.tail,
+                                 label_smoothing=self._eps, labels=self.labels, ctrl=self.ctrl, rows=self.xent_rows)
+            C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
         else:
             H.softmax_xent(self.logits, self.labels, self.K, 1.0 / B, self.dlogits, self.tail, ctrl=self.ctrl,
                            rows=self.xent_rows)
             C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
 
-    def _stage(self, x, y=None):
+    def _stage(self, x, y=None, dense=False):
         """Upload the call's inputs into (grown-only) device buffers; (re)capture happens
-        only when a buffer had to be reallocated."""
+        only when a buffer had to be reallocated.  ``dense``: y holds [n, K] target rows,
+        kept as a float buffer (the class-id buffer is then all zeros)."""
         n = len(x)
         h, w, c = self.in_shape
         x = np.asarray(x)
@@ -160,7 +167,18 @@ class NativeInference(NativeGraphEngine):
         if yb is None or yb.shape[0] < n:
             self._bufs["y"] = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
             realloc = True
-        if y is not None:
+        if y is not None and dense:
+            y = np.asarray(y)
+            if y.ndim != 2 or y.shape[1] != self.K:
+                raise ValueError(f"{type(self.model.loss).__name__} takes one-hot / dense targets of shape "
+                                 f"(n, {self.K}) for this model, got y of shape {tuple(y.shape)}")
+            yd = self._bufs.get("yd")
+            if yd is None or yd.shape[0] < n:
+                self._bufs["yd"] = torch.zeros((max(n, 1), self.K), dtype=torch.float32, device=self.device)
+                realloc = True
+            self._bufs["yd"][:n].copy_(torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)))
+            self._bufs["y"].zero_()
+        elif y is not None:
             self._bufs["y"][:n].copy_(torch.from_numpy(np.asarray(y).astype(np.int32).reshape(n)))
         ob = self._bufs.get("out")
         if ob is None or ob.shape[0] < n:
@@ -212,10 +230,16 @@ class NativeInference(NativeGraphEngine):
     @torch.no_grad()
     def evaluate_sums(self, x, y) -> Tuple[float, float, float]:
         """(sum of per-sample loss, number of samples, number correct) over (x, y)."""
-        n = self._stage(x, y)
+        dense = dense_targets(self.model)
+        n = self._stage(x, y, dense=dense)
         if n == 0:
             return 0.0, 0.0, 0.0
-        self._run("evaluate", n)
+        if dense:
+            eps = float(self.model.loss.label_smoothing or 0.0)
+            if eps != getattr(self, "_eps", None):  # a kernel argument of the captured step
+                self._eps = eps
+                self._graphs.pop("evaluate_dense", None)
+        self._run("evaluate_dense" if dense else "evaluate", n)
         c = self.ctrl.cpu().tolist()
         return _i2f(c[C_AL]), _i2f(c[C_AN]), _i2f(c[C_AC])
 

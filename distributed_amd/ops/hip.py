@@ -1043,6 +1043,57 @@ def softmax_xent(logits, labels, K, scale, dlogits, tail, ctrl=None, rows=None, 
                       _ptr(rows), stream_handle(), bias_grad=_ptr(bias_grad))
 
 
+def softmax_xent_dense(logits, targets, K, scale, dlogits, tail, label_smoothing=0.0, labels=None, ctrl=None,
+                       rows=None, bias_grad=None):
+    """:func:`softmax_xent` against dense fp32 target rows ``[n, K]`` (one-hot or soft) with
+    Keras label smoothing: loss = -sum y' log softmax, dlogits = (softmax * sum y' - y') *
+    scale, correct = argmax logits == argmax targets.  Without ``ctrl`` row b of ``targets``
+    belongs to logits row b; with ``ctrl`` the kernel reads row ``cursor * global_batch +
+    row0 + b`` of the epoch-ordered targets (modulo nsamples in wrap mode) and ``labels``
+    (int32 [B], >= 0 real / < 0 past the end of the data) is required."""
+    B, ld = logits.shape
+    _chk(logits, torch.float32, "logits")
+    _chk(targets, torch.float32, "targets")
+    if targets.dim() != 2 or targets.shape[1] != K:
+        raise ValueError(f"softmax_xent_dense: targets must be [n, {K}], got {tuple(targets.shape)}")
+    if K > ld or tuple(dlogits.shape) != (B, ld):
+        raise ValueError("softmax_xent_dense: dlogits must share the logits' shape and K <= row pitch")
+    _chk(dlogits, torch.bfloat16, "dlogits")
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f"softmax_xent_dense: label_smoothing {label_smoothing} not in [0, 1)")
+    if ctrl is None and targets.shape[0] < B:
+        raise ValueError(f"softmax_xent_dense: {B} logits rows but {targets.shape[0]} target rows")
+    if labels is not None:
+        _chk(labels, torch.int32, "labels")
+        if labels.numel() < B:
+            raise ValueError("softmax_xent_dense: labels needs one entry per logits row")
+    elif ctrl is not None:
+        raise ValueError("softmax_xent_dense: ctrl addressing needs the step's labels (row validity)")
+    if rows is None:
+        rows = xent_rows(B, logits.device)  # (eager callers only: engines pass their own)
+    if bias_grad is not None:
+        _chk(bias_grad, torch.float32, "bias_grad")
+        if bias_grad.numel() < K or not softmax_bias_fold_ok(B, K):
+            raise ValueError("softmax_xent_dense: bias_grad needs >= K floats and a one-split colsum shape")
+    _C().softmax_xent_dense(_ptr(logits), ld, _ptr(labels), _ptr(targets), B, K, float(label_smoothing), float(scale),
+                            _ptr(ctrl), _ptr(dlogits), _ptr(tail), _ptr(rows), stream_handle(),
+                            bias_grad=_ptr(bias_grad))
+
+
+def softmax_store(logits, K, ctrl, out):
+    """out[global row] = softmax(logits row) for the rows of the step at the device cursor
+    (``ctrl``) that exist; ``out`` is fp32 ``[n, K]`` with n >= ctrl's nsamples."""
+    B, ld = logits.shape
+    _chk(logits, torch.float32, "logits")
+    _chk(out, torch.float32, "out")
+    _chk(ctrl, torch.int32, "ctrl")
+    if K > ld or out.dim() != 2 or out.shape[1] != K:
+        raise ValueError(f"softmax_store: out must be [n, {K}] and K <= the logits' row pitch {ld}")
+    if ctrl.numel() < 32:
+        raise ValueError("softmax_store: ctrl is the 32-word device control block")
+    _C().softmax_store(_ptr(logits), ld, K, B, _ptr(ctrl), _ptr(out), stream_handle())
+
+
 def softmax_bias_fold_ok(B: int, K: int) -> bool:
     """colsum of a [B][K] gradient runs as one split (the order softmax_xent reproduces)."""
     return _C().colsum_splits(B, K) == 1

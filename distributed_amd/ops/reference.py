@@ -86,6 +86,20 @@ def sparse_softmax_xent(logits, labels):
     return F.cross_entropy(logits.float(), labels.long(), reduction="none")
 
 
+def softmax_xent_dense(logits, targets, label_smoothing=0.0):
+    """Per-sample loss of CategoricalCrossentropy(from_logits=True, label_smoothing) against
+    dense target rows: -(y' * log_softmax(z)).sum(-1), y' = y (1 - eps) + eps / K."""
+    y = targets.float()
+    if label_smoothing:
+        y = y * (1.0 - label_smoothing) + label_smoothing / y.shape[-1]
+    return -(y * torch.log_softmax(logits.float(), dim=-1)).sum(-1)
+
+
+def categorical_accuracy(logits, targets):
+    """Per-sample 0/1 of categorical accuracy (both argmaxes: ties -> first index)."""
+    return (logits.argmax(dim=-1) == targets.argmax(dim=-1)).float()
+
+
 def sparse_accuracy(logits, labels):
     """Per-sample 0/1 of sparse categorical accuracy (argmax ties -> first index)."""
     return (logits.argmax(dim=-1) == labels.long()).float()

@@ -63,6 +63,11 @@ def array_reshape(x, dim, order: str = "C"):
     return np.reshape(np.asarray(x), tuple(int(d) for d in dim), order=order)
 
 
+def to_categorical(y, num_classes=None, dtype: str = "float32"):
+    """R keras ``to_categorical``: class ids -> one-hot rows (for ``categorical_crossentropy``)."""
+    return _keras.utils.to_categorical(y, None if num_classes is None else int(num_classes), dtype)
+
+
 # ---- model construction ----------------------------------------------------------------
 def keras_model_sequential(layers=None, name=None):
     return _keras.Sequential(layers, name=name)
