@@ -73,6 +73,16 @@ layer_activation <- function(object = NULL, activation, name = NULL) {
   .r()$layer_activation(object, activation = activation, name = name)
 }
 
+# Weight regularizers, e.g. layer_dense(units = 10, kernel_regularizer = regularizer_l2(1e-4))
+#' @export
+regularizer_l1 <- function(l = 0.01) .r()$regularizer_l1(l = l)
+
+#' @export
+regularizer_l2 <- function(l = 0.01) .r()$regularizer_l2(l = l)
+
+#' @export
+regularizer_l1_l2 <- function(l1 = 0.01, l2 = 0.01) .r()$regularizer_l1_l2(l1 = l1, l2 = l2)
+
 #' @export
 compile <- function(object, optimizer = NULL, loss = NULL, metrics = NULL, ...) {
   invisible(.tag(.r()$compile(object, optimizer = optimizer, loss = loss, metrics = metrics, ...)))

@@ -175,8 +175,25 @@ struct OptArgs {
   float b1, b2, eps, rho, mom;
   int flag;
 };
+// reg (optional): the weight-regularizer segment table, nreg rows of 4 words (offset, size,
+// l1 as float bits, l2 as float bits) sorted by offset, 16-byte aligned, nreg <= REG_MAX_ROWS;
+// offsets are absolute in the engine's flat buffer and P[0] is its element `lo`.  Each
+// element of a row uses g + 2 l2 w + l1 sign(w) as its gradient.  reg == nullptr or
+// nreg == 0: the kernel without any regularizer code.
+constexpr int REG_MAX_ROWS = 2048;  // 32 KB of LDS per block
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
-                    const float* tail, const OptArgs& o, hipStream_t s, int book = 1);
+                    const float* tail, const OptArgs& o, hipStream_t s, int book = 1, const int32_t* reg = nullptr,
+                    int nreg = 0, long lo = 0);
+// R = sum over the table's rows of l1 sum|w| + l2 sum(w^2) over the flat fp32 buffer P[n]
+// (n a multiple of 4, P 16-byte aligned, rows starting on 8-element boundaries with zero
+// padding behind them), summed in a fixed order (no float atomics).  scratch holds
+// reg_penalty_blocks(n) + 2 words, zero before the first launch: per-block partials, the
+// arrival counter (re-armed by the launch) and R, which the host may read.  tail (optional):
+// tail[0] += R * tail[2] -- the loss sum of a step gains R for each of its valid rows.
+// nreg == 0 launches nothing.
+int reg_penalty_blocks(long n);
+hipError_t reg_penalty(const float* P, long n, const int32_t* reg, int nreg, float* scratch, float* tail,
+                       hipStream_t s);
 
 // Data / layout glue -------------------------------------------------------------------------
 // the step's rows of the (epoch-permuted) dataset: row = (cursor*global_batch + row0 + i)

@@ -2037,17 +2037,61 @@ __global__ __launch_bounds__(NT) void unpad_add_k(const float* src, int R, int C
 // native-engine counterpart of keras/optimizers.py apply_flat.  lr from ctrl (a schedule
 // needs no re-capture); Adam's step t = ctrl->cur3, written by gather_batch at the start
 // of the step (no block of this kernel reads a ctrl field this kernel writes).
+//
+// Weight regularizers (REG): a segment table, one row (offset, size, l1 bits, l2 bits) per
+// regularized variable, sorted by offset; offsets index the engine's whole flat buffer and
+// element 0 of this launch is element `lo` of it (per-bucket launches).  The block stages
+// the table into LDS once; each thread finds the row of its element by a binary search
+// there (the row found last is tried first) and uses g = G[i] + (2 l2 w + l1 sign(w)),
+// sign(0) = 0, formed from the fp32 master AFTER the all-reduce: counted once whatever the
+// world size, exact under bf16 gradient buckets.  REG = false is the kernel without any of it.
+struct RegSeg {
+  int off, end;  // [off, end) of the flat buffer; off > end: none
+  float l1, l2;
+};
+// the row covering element i of a table of nreg rows (LDS), or an empty one
+__device__ __forceinline__ RegSeg reg_find(const int4* tab, int nreg, long i) {
+  int a = 0, b = nreg;  // the last row with offset <= i is a - 1
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    if ((long)tab[m].x <= i) a = m + 1; else b = m;
+  }
+  RegSeg r{1, 0, 0.f, 0.f};
+  if (a > 0) {
+    const int4 q = tab[a - 1];
+    if (i < (long)q.x + q.y) r = RegSeg{q.x, q.x + q.y, __int_as_float(q.z), __int_as_float(q.w)};
+  }
+  return r;
+}
+__device__ __forceinline__ void reg_stage(int4* lds, const int4* tab, int nreg) {
+  for (int r = threadIdx.x; r < nreg; r += NT) lds[r] = tab[r];
+  __syncthreads();
+}
+
+template <bool REG>
 __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const float* __restrict__ G,
                                                  float* __restrict__ S0, float* __restrict__ S1,
                                                  float* __restrict__ S2, uint16_t* __restrict__ Pb, long n,
-                                                 Ctrl* ctrl, const float* tail, OptArgs o, int book) {
+                                                 Ctrl* ctrl, const float* tail, OptArgs o, int book,
+                                                 const int4* reg, int nreg, long lo) {
+  extern __shared__ __attribute__((aligned(16))) int4 reg_lds[];
+  RegSeg seg{1, 0, 0.f, 0.f};
+  if constexpr (REG) reg_stage(reg_lds, reg, nreg);
   const float lr = ctrl->lr;
   const int t = ctrl->cur3;
   float lr_t = lr;
   if (o.kind == 1) lr_t = lr * sqrtf(1.f - powf(o.b2, (float)t)) / (1.f - powf(o.b1, (float)t));
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
-    const float g = G[i];
+    float g = G[i];
     float w = P[i];
+    if constexpr (REG) {
+      const long a = lo + i;
+      if (a < seg.off || a >= seg.end) seg = reg_find(reg_lds, nreg, a);
+      if (a >= seg.off && a < seg.end) {
+        const float sgn = (float)((w > 0.f) - (w < 0.f));
+        g += fmaf(2.f * seg.l2, w, seg.l1 * sgn);
+      }
+    }
     if (o.kind == 1) {  // Adam (S0 m, S1 v, S2 vhat)
       const float m = o.b1 * S0[i] + (1.f - o.b1) * g;
       const float v = o.b2 * S1[i] + (1.f - o.b2) * g * g;
@@ -2100,10 +2144,108 @@ __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const fl
 }
 
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
-                    const float* tail, const OptArgs& o, hipStream_t s, int book) {
+                    const float* tail, const OptArgs& o, hipStream_t s, int book, const int32_t* reg, int nreg,
+                    long lo) {
   if (o.kind < 0 || o.kind > 2 || n < 0) return hipErrorInvalidValue;
   const int grid = n > 0 ? grid_for(n, NT, 4096) : 1;
-  hipLaunchKernelGGL(opt_step_k, dim3(grid), dim3(NT), 0, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book);
+  if (reg == nullptr || nreg == 0) {
+    hipLaunchKernelGGL(opt_step_k<false>, dim3(grid), dim3(NT), 0, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book,
+                       nullptr, 0, 0L);
+    return hipGetLastError();
+  }
+  if (nreg < 0 || nreg > REG_MAX_ROWS || lo < 0 || (reinterpret_cast<uintptr_t>(reg) & 15)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(opt_step_k<true>, dim3(grid), dim3(NT), nreg * sizeof(int4), s, P, G, S0, S1, S2, Pb, n, ctrl,
+                     tail, o, book, reinterpret_cast<const int4*>(reg), nreg, lo);
+  return hipGetLastError();
+}
+
+// R = sum over the table's rows of l1 sum|w| + l2 sum(w^2), in a fixed order: block b owns
+// the 4-element groups [b per, (b + 1) per) of P (per = ceil(groups / grid), the grid a
+// function of n alone); a thread adds its groups (16-byte loads: variables start on
+// 8-element boundaries and the padding behind them is zero, so a group lies in one row)
+// in fp32, then a wave shuffle tree, one LDS exchange, one partial per block.  The last
+// block to arrive adds the partials in block order, re-arms the counter, stores R in
+// scratch[grid + 1] and, with a tail, does tail[0] += R * tail[2] (the step's loss sum gains
+// R per valid local row).  No float atomics: two launches give the same bits.
+// scratch: [grid] partials, [1] arrival counter (int, zero before the first launch), [1] R.
+namespace {
+constexpr int RP_MAX_BLOCKS = 1024, RP_U = 4;
+__global__ __launch_bounds__(NT) void reg_penalty_k(const float* __restrict__ P, long groups, long per,
+                                                    const int4* reg, int nreg, float* scratch, float* tail) {
+  extern __shared__ __attribute__((aligned(16))) int4 reg_lds[];
+  float* wsum = reinterpret_cast<float*>(reg_lds + nreg);  // [SX_NW], then the election flag
+  int* last = reinterpret_cast<int*>(wsum + SX_NW);
+  const int b = blockIdx.x, t = threadIdx.x, nb = gridDim.x, lane = t & 63, w = t >> 6;
+  reg_stage(reg_lds, reg, nreg);
+  RegSeg seg{1, 0, 0.f, 0.f};
+  float acc = 0.f;
+  const long g1 = (b + 1) * per < groups ? (b + 1) * per : groups;
+  // RP_U groups per trip, their loads issued together ahead of the row searches (a small
+  // gain: 25.3 us per launch against 26.0 us with one group per trip over ResNet-18's
+  // 46.7 MB, back-to-back launches in a captured graph); the groups are still added in
+  // ascending order
+  for (long g = b * per + t; g < g1; g += RP_U * NT) {
+    float4 v[RP_U];
+#pragma unroll
+    for (int u = 0; u < RP_U; ++u) {
+      const long gu = g + u * NT;
+      v[u] = gu < g1 ? *reinterpret_cast<const float4*>(P + 4 * gu) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < RP_U; ++u) {
+      const long i = 4 * (g + u * NT);
+      if (g + u * NT >= g1) break;
+      if (i < seg.off || i >= seg.end) seg = reg_find(reg_lds, nreg, i);
+      if (i >= seg.off && i < seg.end) {
+        const float s1 = (fabsf(v[u].x) + fabsf(v[u].y)) + (fabsf(v[u].z) + fabsf(v[u].w));
+        const float s2 = (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
+        acc += seg.l1 * s1 + seg.l2 * s2;
+      }
+    }
+  }
+  acc = sx_wave_sum(acc);
+  if (lane == 0) wsum[w] = acc;
+  __syncthreads();
+  if (t == 0) {
+    float v = wsum[0];
+#pragma unroll
+    for (int u = 1; u < SX_NW; ++u) v += wsum[u];
+    scratch[b] = v;
+  }
+  int* counter = reinterpret_cast<int*>(scratch + nb);
+  if (!last_arriver(counter, nb, last)) return;
+  float a = 0.f;
+  for (int r = t; r < nb; r += NT) a += scratch[r];
+  a = sx_wave_sum(a);
+  if (lane == 0) wsum[w] = a;
+  __syncthreads();
+  if (t == 0) {
+    float R = wsum[0];
+#pragma unroll
+    for (int u = 1; u < SX_NW; ++u) R += wsum[u];
+    scratch[nb + 1] = R;
+    if (tail) tail[0] += R * tail[2];
+    *counter = 0;
+  }
+}
+}  // namespace
+
+int reg_penalty_blocks(long n) {
+  const long groups = n / 4, want = (groups + 4L * NT - 1) / (4L * NT);
+  return (int)(want < 1 ? 1 : want > RP_MAX_BLOCKS ? RP_MAX_BLOCKS : want);
+}
+
+hipError_t reg_penalty(const float* P, long n, const int32_t* reg, int nreg, float* scratch, float* tail,
+                       hipStream_t s) {
+  if (n < 0 || n % 4 || nreg < 0 || nreg > REG_MAX_ROWS || scratch == nullptr) return hipErrorInvalidValue;
+  if (nreg == 0 || n == 0) return hipSuccess;  // R = 0: nothing to add
+  if (reg == nullptr || ((reinterpret_cast<uintptr_t>(reg) | reinterpret_cast<uintptr_t>(P)) & 15))
+    return hipErrorInvalidValue;
+  const int grid = reg_penalty_blocks(n);
+  const long groups = n / 4, per = (groups + grid - 1) / grid;
+  const size_t lds = nreg * sizeof(int4) + (SX_NW + 1) * sizeof(float);
+  hipLaunchKernelGGL(reg_penalty_k, dim3(grid), dim3(NT), lds, s, P, groups, per, reinterpret_cast<const int4*>(reg),
+                     nreg, scratch, tail);
   return hipGetLastError();
 }
 

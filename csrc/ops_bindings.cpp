@@ -359,14 +359,23 @@ void register_kernel_ops(py::module_& m) {
           "sgd_step");
   });
   m.def("opt_step", [](U P, U G, U S0, U S1, U S2, U Pb, long n, U ctrl, U tail, int kind, float b1, float b2,
-                       float eps, float rho, float mom, int flag, U s, int book) {
+                       float eps, float rho, float mom, int flag, U s, int book, U reg, int nreg, long lo) {
     damd::OptArgs o{kind, b1, b2, eps, rho, mom, flag};
     check(damd::opt_step(P_<float>(P), P_<const float>(G), P_<float>(S0), P_<float>(S1), P_<float>(S2), P_<u16>(Pb), n,
-                         P_<damd::Ctrl>(ctrl), P_<const float>(tail), o, P_<ihipStream_t>(s), book),
+                         P_<damd::Ctrl>(ctrl), P_<const float>(tail), o, P_<ihipStream_t>(s), book,
+                         P_<const int32_t>(reg), nreg, lo),
           "opt_step");
   }, py::arg("P"), py::arg("G"), py::arg("S0"), py::arg("S1"), py::arg("S2"), py::arg("Pb"), py::arg("n"),
      py::arg("ctrl"), py::arg("tail"), py::arg("kind"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("rho"),
-     py::arg("mom"), py::arg("flag"), py::arg("s"), py::arg("book") = 1);
+     py::arg("mom"), py::arg("flag"), py::arg("s"), py::arg("book") = 1, py::arg("reg") = 0, py::arg("nreg") = 0,
+     py::arg("lo") = 0);
+  m.attr("REG_MAX_ROWS") = damd::REG_MAX_ROWS;
+  m.def("reg_penalty_blocks", &damd::reg_penalty_blocks);
+  m.def("reg_penalty", [](U P, long n, U reg, int nreg, U scratch, U tail, U s) {
+    check(damd::reg_penalty(P_<const float>(P), n, P_<const int32_t>(reg), nreg, P_<float>(scratch), P_<float>(tail),
+                            P_<ihipStream_t>(s)),
+          "reg_penalty");
+  });
   m.def("gather_batch", [](U x, int x_u8, float scale, U labels, U ctrl, int per, int HW, int Cin, int Cp, U xb, U yb,
                            U s, U zero, long zero_bytes, U zero2, long zero2_bytes, U pc_src, U pc_dst,
                            std::vector<int> pc_dims) {

@@ -53,6 +53,51 @@ class GenericEngine(Engine):
         self.feed = None
         self.step_in_epoch = 0
         self._plan_buckets()
+        self._plan_regularizers()
+
+    def _plan_regularizers(self):
+        """Weight penalties (keras/regularizers.py).  L1L2 on a trainable variable: a row
+        (offset, size, l1, l2) of ``reg_table`` over the flat buffer, closed form
+        (ops/reference.py reg_grad / reg_penalty).  Any other callable: evaluated and
+        differentiated with torch.  A frozen layer's regularizer adds to the loss only."""
+        from ..keras import regularizers as _regs
+
+        idx = {id(v): i for i, v in enumerate(self.vars)}
+        self.reg_table, self.reg_other, self.reg_frozen = [], [], []
+        for v, r in self.model._regularized():
+            i, co = idx.get(id(v)), _regs.coefficients(r)
+            if i is None:
+                self.reg_frozen.append((v, r))
+            elif co is not None:
+                self.reg_table.append((self.offs[i], self.sizes[i], co[0], co[1]))
+            else:
+                self.reg_other.append((i, r))
+        self.regularized = bool(self.reg_table or self.reg_other or self.reg_frozen)
+
+    @torch.no_grad()
+    def _reg_penalty(self):
+        """R at the current weights (fp32 scalar on the device)."""
+        from ..ops import reference
+
+        r = reference.reg_penalty(self.P, self.reg_table)
+        for i, f in self.reg_other:
+            r = r + f(self.leaves[i].detach()).float()
+        for v, f in self.reg_frozen:
+            r = r + f(v.value.detach()).float().to(r.device)
+        return r
+
+    def _add_reg_grad(self, g):
+        """g (the all-reduced flat gradient) += dR/dw: once per step, whatever the world size."""
+        from ..ops import reference
+
+        with torch.no_grad():
+            if self.reg_table:
+                g += reference.reg_grad(self.P, self.reg_table)
+        for i, f in self.reg_other:
+            (d,) = torch.autograd.grad(f(self.leaves[i]), self.leaves[i], allow_unused=True)
+            if d is not None:
+                with torch.no_grad():
+                    g[self.offs[i]:self.offs[i] + self.sizes[i]] += d.reshape(-1)
 
     def _plan_buckets(self):
         """Gradient buckets (SURVEY.md §3.3 / N3'): contiguous ranges of G filled from the
@@ -149,6 +194,8 @@ class GenericEngine(Engine):
             self._tick("forward")
             with torch.no_grad():
                 G[self.n] = ls.detach().sum()
+                if self.regularized:  # the SUM all-reduce then yields R * (global rows)
+                    G[self.n] += self._reg_penalty() * float(idx.numel())
                 G[self.n + 1] = float(idx.numel())
                 for i, m in enumerate(self.metric_objs):
                     G[self.n + 2 + i] = m.per_sample(yb, out.detach()).sum()
@@ -171,6 +218,8 @@ class GenericEngine(Engine):
         elif self.world > 1:
             self.strategy.communicator.allreduce_(G, "sum")
         self._tick("allreduce")
+        if self.regularized:
+            self._add_reg_grad(G[: self.n])
         self.model.optimizer.apply_flat(self.P, G[: self.n])
         self.acc += G[self.n:].double()
         self.step_in_epoch += 1

@@ -191,6 +191,33 @@ def _param_weights(model):
     return out
 
 
+def reg_rows(variables, offsets):
+    """Segment-table rows (offset, size, l1, l2) of the L1L2-regularized ``variables`` laid
+    out at ``offsets`` of a flat buffer (an L1L2 with both coefficients 0 has no row)."""
+    from ..keras import regularizers as _regs
+
+    rows = []
+    for v, off in zip(variables, offsets):
+        co = _regs.coefficients(getattr(v, "regularizer", None))
+        if co is not None and (co[0] or co[1]):
+            rows.append((off, int(np.prod(v.shape)), co[0], co[1]))
+    return rows
+
+
+def regularizers_ok(model):
+    """(ok, reason): every weight penalty of ``model`` is an L1L2 (the closed form the
+    opt_step / reg_penalty kernels implement) and they fit the segment table."""
+    from ..keras import regularizers as _regs
+
+    regs = model._regularized()
+    for v, r in regs:
+        if _regs.coefficients(r) is None:
+            return False, f"regularizer {_regs.name_of(r)}"
+    if len(regs) > H.REG_MAX_ROWS:
+        return False, f"regularizers: {len(regs)} segments exceed the table cap {H.REG_MAX_ROWS}"
+    return True, ""
+
+
 def _opt_kernel_slots(opt):
     """(opt_step kind, slot names for S0..S2; '' = unused) of a Keras optimizer."""
     from ..keras import optimizers
@@ -234,6 +261,9 @@ class NativeGraphEngine(Engine):
         if any(id(w) not in trainable for w in _param_weights(model)):
             return False, "frozen layer weights"
         ok, why = NativeGraphEngine.layers_eligible(model)
+        if not ok:
+            return ok, why
+        ok, why = regularizers_ok(model)
         if not ok:
             return ok, why
         return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
@@ -319,6 +349,11 @@ class NativeGraphEngine(Engine):
             self.bviews[id(v)] = self.Pb[off:off + sz].view(v.shape)
             self.gviews[id(v)] = self.G[off:off + sz].view(v.shape)
         self._own_variables(self.vars)
+        # weight regularizers: the segment table of opt_step / reg_penalty, built once (None:
+        # no regularizer -- nothing is launched for them and opt_step runs without the table)
+        rows = reg_rows(self.vars, offs)
+        self.reg_tab = H.reg_table(rows, dev) if rows else None
+        self.reg_scratch = H.reg_scratch(n, dev) if rows else None
         # non-trainable (BN moving statistics) live on the device as fp32
         for w in model.non_trainable_weights:
             if w.value.device != dev:
@@ -467,6 +502,8 @@ class NativeGraphEngine(Engine):
             "add_fused_bn": sum(1 for nd in self.nodes if nd.attrs.get("fused") and nd.attrs["fused"][1][0] == "bn"),
             "add_relu": sum(1 for nd in self.nodes if nd.kind == "Add" and nd.attrs.get("relu")),
             "dead": sum(1 for nd in self.nodes if nd.attrs.get("dead")),
+            # rows of the weight-regularizer segment table (one per L1L2-regularized variable)
+            "reg_segments": len(reg_rows(self.model.trainable_weights, range(len(self.model.trainable_weights)))),
         }
 
     def _build(self):
@@ -1086,6 +1123,10 @@ class NativeGraphEngine(Engine):
         else:
             H.softmax_xent(self.logits, self.labels, self.K, 1.0 / self.global_batch, self.dlogits,
                            self.G[self.nparam:], ctrl=self.ctrl, rows=self.xent_rows, bias_grad=bias_grad)
+        if self.reg_tab is not None:
+            # loss sum += R(w) per valid local row (tail[2]), before the tail leaves with
+            # bucket 0's all-reduce: the SUM over replicas yields R * (global rows)
+            H.reg_penalty(self.P, self.reg_tab, self.reg_scratch, tail=self.G[self.nparam:])
         self._mark("forward")
         for t in self._all_tensors():
             t.root().written = False
@@ -1121,7 +1162,9 @@ class NativeGraphEngine(Engine):
         o4 = 4 * lo
         self.C.opt_step(self.P.data_ptr() + o4, self.G.data_ptr() + o4, ptr[0] + o4, ptr[1] + o4, ptr[2] + o4,
                         self.Pb.data_ptr() + 2 * lo, max(hi - lo, 0), self.ctrl.data_ptr(),
-                        self.G[self.nparam:].data_ptr(), self.opt_kind, *args, H.stream_handle(), book=book)
+                        self.G[self.nparam:].data_ptr(), self.opt_kind, *args, H.stream_handle(), book=book,
+                        reg=self.reg_tab.data_ptr() if self.reg_tab is not None else 0,
+                        nreg=self.reg_tab.shape[0] if self.reg_tab is not None else 0, lo=lo)
 
     # forward ops
     def _w(self, nd, var):

@@ -31,7 +31,8 @@ import torch
 from ..ops import hip as H
 from ..utils import logging as dlog
 from .native_graph import (C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, NativeGraphEngine, _i2f,
-                           _layer_graph, _pad8, _param_weights, dense_targets, loss_head_ok, output_head)
+                           _layer_graph, _pad8, _param_weights, dense_targets, loss_head_ok, output_head,
+                           reg_rows, regularizers_ok)
 
 
 class NativeInference(NativeGraphEngine):
@@ -45,6 +46,9 @@ class NativeInference(NativeGraphEngine):
             return False, "not on a GPU"
         ok, why = NativeGraphEngine.layers_eligible(model)
         if ok and evaluate:  # (predict uses no loss: its eligibility is the layers' alone)
+            ok, why = regularizers_ok(model)
+            if not ok:
+                return ok, why
             return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
         return ok, why
 
@@ -81,6 +85,10 @@ class NativeInference(NativeGraphEngine):
         for v, sz, o in zip(self.vars, self.sizes, offs):
             self.views[id(v)] = self.P[o:o + sz].view(v.shape)
             self.bviews[id(v)] = self.Pb[o:o + sz].view(v.shape)
+        # weight regularizers (evaluate): R from one reg_penalty launch per call
+        rows = reg_rows(self.vars, offs)
+        self.reg_tab = H.reg_table(rows, dev) if rows else None
+        self.reg_scratch = H.reg_scratch(off, dev) if rows else None
         self.tail = torch.zeros(8, dtype=torch.float32, device=dev)
         self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
@@ -241,7 +249,13 @@ class NativeInference(NativeGraphEngine):
                 self._graphs.pop("evaluate_dense", None)
         self._run("evaluate_dense" if dense else "evaluate", n)
         c = self.ctrl.cpu().tolist()
-        return _i2f(c[C_AL]), _i2f(c[C_AN]), _i2f(c[C_AC])
+        loss, cnt = _i2f(c[C_AL]), _i2f(c[C_AN])
+        if self.reg_tab is not None:
+            # the weights are static during the call: every row's loss gains the same R
+            H.reg_penalty(self.P, self.reg_tab, self.reg_scratch)
+            torch.cuda.synchronize(self.device)
+            loss += float(self.reg_scratch[-1]) * cnt
+        return loss, cnt, _i2f(c[C_AC])
 
 
 def plan_for(model, batch: int, device, evaluate: bool = False):

@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 from . import activations, backend, callbacks, datasets, initializers, layers, losses, metrics, optimizers  # noqa
-from . import utils  # noqa: F401
+from . import regularizers, utils  # noqa: F401
 from .layers import Input  # noqa: F401
 from .models import Model, Sequential  # noqa: F401
 from . import models  # noqa: F401

@@ -10,6 +10,7 @@ ResNet-18 (BASELINE.json:10).
 from __future__ import annotations
 
 import math
+import warnings
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -19,6 +20,7 @@ from .. import ops
 from . import activations as _act
 from . import backend as K
 from . import initializers as _init
+from . import regularizers as _reg
 
 
 def _pair(v):
@@ -36,10 +38,14 @@ def _current_device() -> torch.device:
 class Variable:
     """A named model variable; storage may be relocated into a flat engine buffer."""
 
-    def __init__(self, name: str, value: torch.Tensor, trainable: bool = True, aggregation: str = "none"):
+    def __init__(self, name: str, value: torch.Tensor, trainable: bool = True, aggregation: str = "none",
+                 regularizer=None):
         self.name = name
         self._t = value
         self.trainable = trainable
+        # the weight penalty of this variable (keras/regularizers.py) or None: the engines add
+        # regularizer(value) to the loss and its gradient to the variable's gradient
+        self.regularizer = regularizer
         # tf.VariableAggregation of a mirrored variable read across replicas: "mean" marks
         # the SyncOnRead BN moving statistics (each replica updates its own copy, readers
         # see the replica mean), "none" variables are kept identical by construction
@@ -102,9 +108,18 @@ class KerasTensor:
         return f"<KerasTensor shape={self.shape}>"
 
 
+# accepted for Keras compatibility and not applied: a non-None value warns
+_UNSUPPORTED_KW = ("activity_regularizer", "kernel_constraint", "bias_constraint", "gamma_constraint",
+                   "beta_constraint")
+
+
 class Layer:
     def __init__(self, name: Optional[str] = None, input_shape=None, batch_input_shape=None, trainable=True,
                  dtype=None, **kwargs):
+        for k in _UNSUPPORTED_KW:
+            if kwargs.get(k) is not None:
+                warnings.warn(f"{type(self).__name__}({k}=...) is not supported and has no effect", UserWarning,
+                              stacklevel=3)
         self.name = name or K.unique_name(K.to_snake_case(type(self).__name__))
         self.trainable = trainable
         self.built = False
@@ -119,10 +134,11 @@ class Layer:
         self.output_shape = None
 
     # --- weights -------------------------------------------------------------
-    def add_weight(self, name, shape, initializer="zeros", trainable=True, aggregation="none") -> Variable:
+    def add_weight(self, name, shape, initializer="zeros", trainable=True, aggregation="none",
+                   regularizer=None) -> Variable:
         init = _init.get(initializer)
         val = init(tuple(shape)).to(torch.float32).to(_current_device())
-        v = Variable(f"{self.name}/{name}:0", val, trainable, aggregation)
+        v = Variable(f"{self.name}/{name}:0", val, trainable, aggregation, _reg.get(regularizer))
         self._weights.append(v)
         return v
 
@@ -150,6 +166,13 @@ class Layer:
 
     def count_params(self) -> int:
         return int(sum(int(np.prod(w.shape)) for w in self.weights))
+
+    @property
+    def losses(self) -> List[torch.Tensor]:
+        """The current weight-penalty scalars, one per regularized variable (a frozen
+        layer's too, as in tf.keras)."""
+        with torch.no_grad():
+            return [r(v.value.detach()) for v, r in _reg.regularized(self._weights)]
 
     # --- build / call ----------------------------------------------------------
     def build(self, input_shape):
@@ -214,8 +237,10 @@ def Input(shape, batch_size=None, name=None):  # noqa: N802
 class Conv2D(Layer):
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None, dilation_rate=(1, 1),
                  activation=None, use_bias=True, kernel_initializer="glorot_uniform", bias_initializer="zeros",
-                 **kw):
+                 kernel_regularizer=None, bias_regularizer=None, **kw):
         super().__init__(**kw)
+        self.kernel_regularizer = _reg.get(kernel_regularizer)
+        self.bias_regularizer = _reg.get(bias_regularizer)
         if data_format not in (None, "channels_last"):
             raise ValueError("only channels_last (NHWC) is supported, as in the reference")
         self.filters = int(filters)
@@ -232,8 +257,10 @@ class Conv2D(Layer):
 
     def build(self, input_shape):
         cin = int(input_shape[-1])
-        self.kernel = self.add_weight("kernel", self.kernel_size + (cin, self.filters), self.kernel_initializer)
-        self.bias = self.add_weight("bias", (self.filters,), self.bias_initializer) if self.use_bias else None
+        self.kernel = self.add_weight("kernel", self.kernel_size + (cin, self.filters), self.kernel_initializer,
+                                      regularizer=self.kernel_regularizer)
+        self.bias = (self.add_weight("bias", (self.filters,), self.bias_initializer,
+                                     regularizer=self.bias_regularizer) if self.use_bias else None)
 
     def compute_output_shape(self, s):
         n, h, w, _ = s
@@ -256,7 +283,8 @@ class Conv2D(Layer):
                  activation=_act.serialize(self.activation), use_bias=self.use_bias,
                  kernel_initializer=_init.serialize(self.kernel_initializer),
                  bias_initializer=_init.serialize(self.bias_initializer),
-                 kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 kernel_regularizer=_reg.serialize(self.kernel_regularizer),
+                 bias_regularizer=_reg.serialize(self.bias_regularizer), activity_regularizer=None,
                  kernel_constraint=None, bias_constraint=None)
         return c
 
@@ -350,8 +378,10 @@ class Reshape(Layer):
 
 class Dense(Layer):
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer="glorot_uniform",
-                 bias_initializer="zeros", **kw):
+                 bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None, **kw):
         super().__init__(**kw)
+        self.kernel_regularizer = _reg.get(kernel_regularizer)
+        self.bias_regularizer = _reg.get(bias_regularizer)
         self.units = int(units)
         self.activation = _act.get(activation)
         self.use_bias = use_bias
@@ -362,8 +392,10 @@ class Dense(Layer):
 
     def build(self, input_shape):
         fin = int(input_shape[-1])
-        self.kernel = self.add_weight("kernel", (fin, self.units), self.kernel_initializer)
-        self.bias = self.add_weight("bias", (self.units,), self.bias_initializer) if self.use_bias else None
+        self.kernel = self.add_weight("kernel", (fin, self.units), self.kernel_initializer,
+                                      regularizer=self.kernel_regularizer)
+        self.bias = (self.add_weight("bias", (self.units,), self.bias_initializer,
+                                     regularizer=self.bias_regularizer) if self.use_bias else None)
 
     def compute_output_shape(self, s):
         return tuple(s[:-1]) + (self.units,)
@@ -377,7 +409,8 @@ class Dense(Layer):
         c.update(units=self.units, activation=_act.serialize(self.activation), use_bias=self.use_bias,
                  kernel_initializer=_init.serialize(self.kernel_initializer),
                  bias_initializer=_init.serialize(self.bias_initializer),
-                 kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 kernel_regularizer=_reg.serialize(self.kernel_regularizer),
+                 bias_regularizer=_reg.serialize(self.bias_regularizer), activity_regularizer=None,
                  kernel_constraint=None, bias_constraint=None)
         return c
 
@@ -397,6 +430,9 @@ class Activation(Layer):
 
 
 class ReLU(Layer):
+    # the plain rectifier only: the options the engines' planners look at, at their Keras defaults
+    max_value, negative_slope, threshold = None, 0.0, 0.0
+
     def call(self, x, training=False):
         return torch.relu(x)
 
@@ -455,14 +491,18 @@ class BatchNormalization(Layer):
     validation, callbacks and checkpoints read them), so every worker holds, saves and
     evaluates with the replica mean."""
 
-    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True, **kw):
+    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True, beta_regularizer=None,
+                 gamma_regularizer=None, **kw):
         super().__init__(**kw)
         self.axis, self.momentum, self.epsilon, self.center, self.scale = axis, momentum, epsilon, center, scale
+        self.beta_regularizer = _reg.get(beta_regularizer)
+        self.gamma_regularizer = _reg.get(gamma_regularizer)
 
     def build(self, input_shape):
         c = int(input_shape[-1])
-        self.gamma = self.add_weight("gamma", (c,), "ones") if self.scale else None
-        self.beta = self.add_weight("beta", (c,), "zeros") if self.center else None
+        self.gamma = (self.add_weight("gamma", (c,), "ones", regularizer=self.gamma_regularizer)
+                      if self.scale else None)
+        self.beta = self.add_weight("beta", (c,), "zeros", regularizer=self.beta_regularizer) if self.center else None
         self.moving_mean = self.add_weight("moving_mean", (c,), "zeros", trainable=False, aggregation="mean")
         self.moving_variance = self.add_weight("moving_variance", (c,), "ones", trainable=False,
                                                aggregation="mean")
@@ -476,7 +516,8 @@ class BatchNormalization(Layer):
     def get_config(self):
         c = super().get_config()
         c.update(axis=self.axis, momentum=self.momentum, epsilon=self.epsilon, center=self.center,
-                 scale=self.scale)
+                 scale=self.scale, beta_regularizer=_reg.serialize(self.beta_regularizer),
+                 gamma_regularizer=_reg.serialize(self.gamma_regularizer))
         return c
 
 

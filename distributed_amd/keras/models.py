@@ -36,6 +36,7 @@ from . import layers as L
 from . import losses as _losses
 from . import metrics as _metrics
 from . import optimizers as _opts
+from . import regularizers as _regs
 
 KERAS_VERSION = "2.2.4-tf"
 
@@ -139,6 +140,19 @@ class Model(L.Layer):
 
     def count_params(self):
         return int(sum(int(np.prod(w.shape)) for w in self.weights))
+
+    @property
+    def losses(self):
+        """The current weight-penalty scalars of every layer, one per regularizer."""
+        self._sync_engine()
+        return [t for l in self.layers for t in l.losses]
+
+    def _regularized(self):
+        """[(variable, regularizer)] over all layers, frozen ones included."""
+        out = []
+        for l in self.layers:
+            out += l._regularized() if isinstance(l, Model) else _regs.regularized(l._weights)
+        return out
 
     def _sync_engine(self):
         if self._engine is not None:
@@ -413,6 +427,9 @@ class Model(L.Layer):
             sums[1] += j - i
             for k, m in enumerate(self.compiled_metrics):
                 sums[2 + k] += float(m.per_sample(yb, out).double().sum())
+        if plan is None and self._regularized():
+            # the weight penalty R is part of every row's loss (the native plan adds it itself)
+            sums[0] += sum(float(r(v.value.detach()).double()) for v, r in self._regularized()) * float(sums[1])
         if world > 1:
             st.communicator.allreduce_(sums, "sum")
         cnt = max(float(sums[1]), 1.0)
@@ -561,8 +578,7 @@ class Sequential(Model):
         return {"name": self.name, "layers": self._layer_configs()}
 
 
-_IGNORED_CFG = ("kernel_regularizer", "bias_regularizer", "activity_regularizer", "kernel_constraint",
-                "bias_constraint", "noise_shape", "seed", "sparse", "ragged")
+_IGNORED_CFG = ("noise_shape", "seed", "sparse", "ragged")
 
 
 def _layer_from_config(lc: dict) -> L.Layer:
@@ -573,6 +589,9 @@ def _layer_from_config(lc: dict) -> L.Layer:
     cfg.pop("dtype", None)
     for k in _IGNORED_CFG:
         cfg.pop(k, None)
+    for k in L._UNSUPPORTED_KW:  # (a non-None value reaches the layer, which warns)
+        if cfg.get(k) is None:
+            cfg.pop(k, None)
     if "batch_input_shape" in cfg:
         cfg["input_shape"] = tuple(cfg.pop("batch_input_shape")[1:])
     return cls(**cfg)

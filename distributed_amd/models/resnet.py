@@ -9,39 +9,46 @@ shortcuts) -> GlobalAveragePooling -> Dense(classes) logits.  Convs have no bias
 11,689,512 trainable parameters at 1000 classes (+ 9,600 BN moving statistics).
 
 ``widths``/``blocks``/``input_shape`` shrink it for tests; the graph shape stays the same.
+``weight_decay`` puts ``regularizers.l2(weight_decay)`` on every conv and dense kernel (the
+usual Keras ResNet recipe); None (default) builds the model without regularizers.
 """
 from __future__ import annotations
 
 
-def _basic_block(x, filters, stride, name, layers):
+def _basic_block(x, filters, stride, name, layers, reg=None):
     shortcut = x
-    y = layers.Conv2D(filters, 3, strides=stride, padding="same", use_bias=False, name=f"{name}_conv1")(x)
+    y = layers.Conv2D(filters, 3, strides=stride, padding="same", use_bias=False, kernel_regularizer=reg,
+                      name=f"{name}_conv1")(x)
     y = layers.BatchNormalization(epsilon=1.001e-5, name=f"{name}_bn1")(y)
     y = layers.Activation("relu", name=f"{name}_relu1")(y)
-    y = layers.Conv2D(filters, 3, padding="same", use_bias=False, name=f"{name}_conv2")(y)
+    y = layers.Conv2D(filters, 3, padding="same", use_bias=False, kernel_regularizer=reg,
+                      name=f"{name}_conv2")(y)
     y = layers.BatchNormalization(epsilon=1.001e-5, name=f"{name}_bn2")(y)
     if stride != 1 or int(x.shape[-1]) != filters:
-        shortcut = layers.Conv2D(filters, 1, strides=stride, use_bias=False, name=f"{name}_proj")(x)
+        shortcut = layers.Conv2D(filters, 1, strides=stride, use_bias=False, kernel_regularizer=reg,
+                                 name=f"{name}_proj")(x)
         shortcut = layers.BatchNormalization(epsilon=1.001e-5, name=f"{name}_proj_bn")(shortcut)
     y = layers.Add(name=f"{name}_add")([y, shortcut])
     return layers.Activation("relu", name=f"{name}_out")(y)
 
 
 def resnet18(classes: int = 1000, input_shape=(224, 224, 3), widths=(64, 128, 256, 512), blocks=(2, 2, 2, 2),
-             name: str = "resnet18"):
-    from ..keras import Model, layers
+             name: str = "resnet18", weight_decay=None):
+    from ..keras import Model, layers, regularizers
 
+    reg = regularizers.l2(weight_decay) if weight_decay is not None else None
     inp = layers.Input(shape=input_shape, name="input_1")
-    x = layers.Conv2D(widths[0], 7, strides=2, padding="same", use_bias=False, name="conv1_conv")(inp)
+    x = layers.Conv2D(widths[0], 7, strides=2, padding="same", use_bias=False, kernel_regularizer=reg,
+                      name="conv1_conv")(inp)
     x = layers.BatchNormalization(epsilon=1.001e-5, name="conv1_bn")(x)
     x = layers.Activation("relu", name="conv1_relu")(x)
     x = layers.MaxPooling2D(3, strides=2, padding="same", name="pool1_pool")(x)
     for si, (w, nb) in enumerate(zip(widths, blocks)):
         for bi in range(nb):
             stride = 2 if (si > 0 and bi == 0) else 1
-            x = _basic_block(x, w, stride, f"conv{si + 2}_block{bi + 1}", layers)
+            x = _basic_block(x, w, stride, f"conv{si + 2}_block{bi + 1}", layers, reg)
     x = layers.GlobalAveragePooling2D(name="avg_pool")(x)
-    out = layers.Dense(classes, name="predictions")(x)
+    out = layers.Dense(classes, kernel_regularizer=reg, name="predictions")(x)
     return Model(inp, out, name=name)
 
 

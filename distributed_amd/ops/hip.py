@@ -1104,6 +1104,65 @@ def sgd_flat(P, G, V, Pb, lr, momentum=0.0, nesterov=False):
                   stream_handle())
 
 
+REG_MAX_ROWS = 2048  # layer_ops.h REG_MAX_ROWS: the segment table is staged whole into LDS
+
+
+def reg_table(rows, device) -> torch.Tensor:
+    """The weight-regularizer segment table of ``opt_step`` / ``reg_penalty`` on the device:
+    int32 [nreg, 4] rows (offset, size, l1 as float bits, l2 as float bits) from host rows
+    ``(offset, size, l1, l2)``, sorted by offset.  Offsets index the flat parameter buffer
+    and must be multiples of 8 (the padding behind a variable is zero); rows may not overlap."""
+    rows = sorted((int(o), int(n), float(a), float(b)) for o, n, a, b in rows)
+    if len(rows) > REG_MAX_ROWS:
+        raise ValueError(f"reg_table: {len(rows)} rows exceed the table cap {REG_MAX_ROWS}")
+    end = 0
+    for o, n, _, _ in rows:
+        if o % 8 or n <= 0 or o < end:
+            raise ValueError(f"reg_table: row (offset {o}, size {n}) is misaligned, empty or overlaps the previous")
+        end = o + n
+    if end >= 2 ** 31:
+        raise ValueError("reg_table: offsets are 32-bit (a flat buffer below 2^31 elements)")
+    t = torch.zeros((max(len(rows), 1), 4), dtype=torch.int32)
+    if rows:
+        t[:len(rows), :2] = torch.tensor([r[:2] for r in rows], dtype=torch.int32)
+        t[:len(rows), 2:] = torch.tensor([r[2:] for r in rows], dtype=torch.float32).view(torch.int32)
+    return t.to(device)[:len(rows)]
+
+
+def reg_scratch(n: int, device) -> torch.Tensor:
+    """reg_penalty's scratch for a flat buffer of n floats: per-block partials, the arrival
+    counter (zeroed once; every launch re-arms it) and R, the last word."""
+    return torch.zeros(_C().reg_penalty_blocks(int(n)) + 2, dtype=torch.float32, device=device)
+
+
+def _chk_reg(P, table, where):
+    _chk(P, torch.float32, "P")
+    _chk(table, torch.int32, "table")
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] > REG_MAX_ROWS:
+        raise ValueError(f"{where}: table must be int32 [nreg <= {REG_MAX_ROWS}, 4] (reg_table)")
+
+
+def reg_penalty(P, table, scratch, tail=None):
+    """R = sum over the table's rows of l1 sum|w| + l2 sum(w^2) over the flat fp32 buffer
+    ``P``, in a fixed order; stored in ``scratch[-1]`` (read it after a sync) and, with
+    ``tail``, ``tail[0] += R * tail[2]``.  A table without rows launches nothing (R = 0)."""
+    _chk_reg(P, table, "reg_penalty")
+    n = P.numel()
+    if n % 4:
+        raise ValueError("reg_penalty: the flat buffer must hold a multiple of 4 floats")
+    _chk(scratch, torch.float32, "scratch")
+    if scratch.numel() != _C().reg_penalty_blocks(n) + 2:
+        raise ValueError("reg_penalty: scratch must come from reg_scratch(P.numel())")
+    if tail is not None:
+        _chk(tail, torch.float32, "tail")
+        if tail.numel() < 3:
+            raise ValueError("reg_penalty: tail holds [loss sum, correct, count, ...]")
+    if table.shape[0] == 0:
+        scratch[-1:].zero_()
+        return
+    _C().reg_penalty(_ptr(P), n, _ptr(table), table.shape[0], _ptr(scratch), _ptr(tail), stream_handle())
+
+
 def cast_bf16(x, y):
     _C().cast_f32_bf16(_ptr(x), _ptr(y), x.numel(), stream_handle())
 

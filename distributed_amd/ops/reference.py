@@ -81,6 +81,26 @@ def batchnorm(x, gamma, beta, mean, var, training, momentum=0.99, eps=1e-3):
     return (x - m) * torch.rsqrt(v + eps) * gamma + beta
 
 
+def reg_grad(P, table):
+    """fp32 gradient of the L1/L2 weight penalty over a flat buffer ``P``: for every row
+    ``(offset, size, l1, l2)`` of ``table``, ``2 * l2 * w + l1 * sign(w)`` (sign(0) = 0) on
+    ``P[offset:offset + size]``; zero elsewhere."""
+    g = torch.zeros_like(P, dtype=torch.float32)
+    for off, size, l1, l2 in table:
+        w = P[int(off):int(off) + int(size)].float()
+        g[int(off):int(off) + int(size)] = 2.0 * float(l2) * w + float(l1) * torch.sign(w)
+    return g
+
+
+def reg_penalty(P, table):
+    """fp32 scalar ``R = sum over rows of l1 * sum|w| + l2 * sum(w^2)`` (rows as reg_grad)."""
+    r = torch.zeros((), dtype=torch.float32, device=P.device)
+    for off, size, l1, l2 in table:
+        w = P[int(off):int(off) + int(size)].float()
+        r = r + float(l1) * w.abs().sum() + float(l2) * (w * w).sum()
+    return r
+
+
 def sparse_softmax_xent(logits, labels):
     """Per-sample loss of SparseCategoricalCrossentropy(from_logits=True)."""
     return F.cross_entropy(logits.float(), labels.long(), reduction="none")

@@ -126,6 +126,19 @@ def layer_activation(object=None, activation=None, name=None):
     return _add(object, _keras.layers.Activation(activation, name=name))
 
 
+# ---- regularizers (R keras: regularizer_l1 / regularizer_l2 / regularizer_l1_l2) ----------------
+def regularizer_l1(l=0.01):  # noqa: E741  (the R argument name)
+    return _keras.regularizers.l1(float(l))
+
+
+def regularizer_l2(l=0.01):  # noqa: E741
+    return _keras.regularizers.l2(float(l))
+
+
+def regularizer_l1_l2(l1=0.01, l2=0.01):
+    return _keras.regularizers.l1_l2(l1=float(l1), l2=float(l2))
+
+
 # ---- compile / fit / evaluate ---------------------------------------------------------------
 def compile(object, optimizer=None, loss=None, metrics=None, **kw):  # noqa: A001  (R verb name)
     object.compile(optimizer=optimizer if optimizer is not None else "rmsprop", loss=loss, metrics=metrics, **kw)
