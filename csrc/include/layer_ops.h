@@ -180,10 +180,37 @@ struct OptArgs {
 // offsets are absolute in the engine's flat buffer and P[0] is its element `lo`.  Each
 // element of a row uses g + 2 l2 w + l1 sign(w) as its gradient.  reg == nullptr or
 // nreg == 0: the kernel without any regularizer code.
+//
+// clip: Keras gradient clipping of that (regularized) gradient before the update rule.
+// 0 none; 1 value: clamp to [-clipc, clipc]; 3 global: g * scales[0]; 2 per variable:
+// g * scales[row], where the table must then list EVERY variable (zero coefficients where
+// there is no regularizer; nreg = the number of variables <= REG_MAX_ROWS) and row is the
+// element's row -- the index grad_norm stores its scales under.  scales: grad_norm's output.
+// clip == 0 is the kernel without any clipping code.
 constexpr int REG_MAX_ROWS = 2048;  // 32 KB of LDS per block
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
                     const float* tail, const OptArgs& o, hipStream_t s, int book = 1, const int32_t* reg = nullptr,
-                    int nreg = 0, long lo = 0);
+                    int nreg = 0, long lo = 0, int clip = 0, float clipc = 0.f, const float* scales = nullptr);
+// The L2 norm of the gradient opt_step consumes -- G, plus 2 l2 w + l1 sign(w) from the
+// masters P where vt has coefficients (P == nullptr: G alone, P is not read) -- per variable
+// (per_variable != 0) or over all variables, and the clipping scale c / max(norm, c): exactly
+// 1.0f up to norm == c (a zero gradient included), NaN for a non-finite norm.  One launch,
+// fixed summation order, no float atomics: repeated launches give the same bits.
+// G / P: n floats (n a multiple of 4 below 2^31, 16-byte aligned); variables start on
+// 8-element boundaries and the padding behind them is ZERO in both buffers -- the kernel
+// reads whole 4-element groups and relies on it, as reg_penalty relies on P's padding.
+// vt: nvar rows (offset, size, l1 bits, l2 bits) sorted by offset, 16-byte aligned, one per
+// variable.  ct: nchunk rows (start, row of vt): every variable cut into chunks of GN_CHUNK
+// elements in ascending order, no chunk spanning two variables.  vfirst: nvar + 1 words, the
+// first chunk of each variable (vfirst[nvar] = nchunk).  scratch: nchunk + 1 words, zero
+// before the first launch (per-chunk partials, the arrival counter the launch re-arms).
+// out: 2 * nout floats, the norms then the scales; nout = nvar (per variable) or 1.
+// The tables live on the device and are trusted: build them with ops/hip.py clip_plan.
+constexpr int GN_CHUNK = 4096;
+int grad_norm_blocks(int nchunk);
+hipError_t grad_norm(const float* G, const float* P, long n, const int32_t* vt, int nvar, const int32_t* ct,
+                     int nchunk, const int32_t* vfirst, int per_variable, float c, float* scratch, float* out,
+                     hipStream_t s);
 // R = sum over the table's rows of l1 sum|w| + l2 sum(w^2) over the flat fp32 buffer P[n]
 // (n a multiple of 4, P 16-byte aligned, rows starting on 8-element boundaries with zero
 // padding behind them), summed in a fixed order (no float atomics).  scratch holds

@@ -2068,15 +2068,35 @@ __device__ __forceinline__ void reg_stage(int4* lds, const int4* tab, int nreg) 
   __syncthreads();
 }
 
-template <bool REG>
+// Gradient clipping (CLIP; keras/optimizers.py), applied to the regularized g before the
+// update rule: CLIP_VALUE clamps g to [-clipc, clipc] (a NaN stays a NaN); CLIP_GLOBAL uses
+// g * scales[0]; CLIP_VAR uses g * scales[row], row = the element's row of the table, which
+// then lists EVERY variable (zero coefficients where there is no regularizer) so that the
+// row index also indexes grad_norm's scale array.  A scale of exactly 1.0f leaves g's bits
+// alone.  CLIP_NONE is the kernel without any of it (no load, no LDS beyond REG's).
+enum : int { CLIP_NONE = 0, CLIP_VALUE = 1, CLIP_VAR = 2, CLIP_GLOBAL = 3 };
+// the index of the row covering element i of a table of nreg rows (LDS), or -1
+__device__ __forceinline__ int reg_find_row(const int4* tab, int nreg, long i) {
+  int a = 0, b = nreg;  // reg_find's search: the last row with offset <= i is a - 1
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    if ((long)tab[m].x <= i) a = m + 1; else b = m;
+  }
+  return (a > 0 && i < (long)tab[a - 1].x + tab[a - 1].y) ? a - 1 : -1;
+}
+
+template <bool REG, int CLIP>
 __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const float* __restrict__ G,
                                                  float* __restrict__ S0, float* __restrict__ S1,
                                                  float* __restrict__ S2, uint16_t* __restrict__ Pb, long n,
                                                  Ctrl* ctrl, const float* tail, OptArgs o, int book,
-                                                 const int4* reg, int nreg, long lo) {
+                                                 const int4* reg, int nreg, long lo, float clipc,
+                                                 const float* __restrict__ scales) {
   extern __shared__ __attribute__((aligned(16))) int4 reg_lds[];
   RegSeg seg{1, 0, 0.f, 0.f};
-  if constexpr (REG) reg_stage(reg_lds, reg, nreg);
+  if constexpr (REG || CLIP == CLIP_VAR) reg_stage(reg_lds, reg, nreg);
+  float gscale = 1.f;  // CLIP_GLOBAL: the one scale; CLIP_VAR: the scale of seg's row
+  if constexpr (CLIP == CLIP_GLOBAL) gscale = scales[0];
   const float lr = ctrl->lr;
   const int t = ctrl->cur3;
   float lr_t = lr;
@@ -2084,7 +2104,23 @@ __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const fl
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
     float g = G[i];
     float w = P[i];
-    if constexpr (REG) {
+    if constexpr (CLIP == CLIP_VAR) {
+      const long a = lo + i;
+      if (a < seg.off || a >= seg.end) {
+        const int row = reg_find_row(reg_lds, nreg, a);
+        seg = RegSeg{1, 0, 0.f, 0.f};
+        gscale = 1.f;  // padding between variables: g = 0, no row
+        if (row >= 0) {
+          const int4 q = reg_lds[row];
+          seg = RegSeg{q.x, q.x + q.y, __int_as_float(q.z), __int_as_float(q.w)};
+          gscale = scales[row];
+        }
+      }
+      if (a >= seg.off && a < seg.end && (seg.l1 != 0.f || seg.l2 != 0.f)) {
+        const float sgn = (float)((w > 0.f) - (w < 0.f));
+        g += fmaf(2.f * seg.l2, w, seg.l1 * sgn);
+      }
+    } else if constexpr (REG) {
       const long a = lo + i;
       if (a < seg.off || a >= seg.end) seg = reg_find(reg_lds, nreg, a);
       if (a >= seg.off && a < seg.end) {
@@ -2092,6 +2128,8 @@ __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const fl
         g += fmaf(2.f * seg.l2, w, seg.l1 * sgn);
       }
     }
+    if constexpr (CLIP == CLIP_VALUE) g = g < -clipc ? -clipc : (g > clipc ? clipc : g);
+    if constexpr (CLIP == CLIP_VAR || CLIP == CLIP_GLOBAL) g *= gscale;
     if (o.kind == 1) {  // Adam (S0 m, S1 v, S2 vhat)
       const float m = o.b1 * S0[i] + (1.f - o.b1) * g;
       const float v = o.b2 * S1[i] + (1.f - o.b2) * g * g;
@@ -2143,19 +2181,46 @@ __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const fl
   }
 }
 
+namespace {
+template <bool REG, int CLIP>
+void opt_step_launch(int grid, size_t lds, hipStream_t s, float* P, const float* G, float* S0, float* S1, float* S2,
+                     uint16_t* Pb, long n, Ctrl* ctrl, const float* tail, const OptArgs& o, int book,
+                     const int32_t* reg, int nreg, long lo, float clipc, const float* scales) {
+  hipLaunchKernelGGL((opt_step_k<REG, CLIP>), dim3(grid), dim3(NT), lds, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o,
+                     book, reinterpret_cast<const int4*>(reg), nreg, lo, clipc, scales);
+}
+}  // namespace
+
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
                     const float* tail, const OptArgs& o, hipStream_t s, int book, const int32_t* reg, int nreg,
-                    long lo) {
+                    long lo, int clip, float clipc, const float* scales) {
   if (o.kind < 0 || o.kind > 2 || n < 0) return hipErrorInvalidValue;
+  if (clip < CLIP_NONE || clip > CLIP_GLOBAL) return hipErrorInvalidValue;
+  if (clip == CLIP_VALUE && !(clipc > 0.f)) return hipErrorInvalidValue;
+  if ((clip == CLIP_VAR || clip == CLIP_GLOBAL) && scales == nullptr) return hipErrorInvalidValue;
   const int grid = n > 0 ? grid_for(n, NT, 4096) : 1;
-  if (reg == nullptr || nreg == 0) {
-    hipLaunchKernelGGL(opt_step_k<false>, dim3(grid), dim3(NT), 0, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book,
-                       nullptr, 0, 0L);
-    return hipGetLastError();
+  const bool table = reg != nullptr && nreg != 0;
+  if (clip == CLIP_VAR && !table) return hipErrorInvalidValue;  // the row index comes from the table
+  if (table && (nreg < 0 || nreg > REG_MAX_ROWS || lo < 0 || (reinterpret_cast<uintptr_t>(reg) & 15)))
+    return hipErrorInvalidValue;
+  const size_t lds = table ? nreg * sizeof(int4) : 0;
+#define DAMD_OPT_STEP(REG_, CLIP_) \
+  opt_step_launch<REG_, CLIP_>(grid, lds, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book, reg, nreg, lo, clipc, scales)
+  if (!table) {
+    switch (clip) {
+      case CLIP_NONE: DAMD_OPT_STEP(false, CLIP_NONE); break;
+      case CLIP_VALUE: DAMD_OPT_STEP(false, CLIP_VALUE); break;
+      default: DAMD_OPT_STEP(false, CLIP_GLOBAL); break;
+    }
+  } else {
+    switch (clip) {
+      case CLIP_NONE: DAMD_OPT_STEP(true, CLIP_NONE); break;
+      case CLIP_VALUE: DAMD_OPT_STEP(true, CLIP_VALUE); break;
+      case CLIP_VAR: DAMD_OPT_STEP(true, CLIP_VAR); break;
+      default: DAMD_OPT_STEP(true, CLIP_GLOBAL); break;
+    }
   }
-  if (nreg < 0 || nreg > REG_MAX_ROWS || lo < 0 || (reinterpret_cast<uintptr_t>(reg) & 15)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(opt_step_k<true>, dim3(grid), dim3(NT), nreg * sizeof(int4), s, P, G, S0, S1, S2, Pb, n, ctrl,
-                     tail, o, book, reinterpret_cast<const int4*>(reg), nreg, lo);
+#undef DAMD_OPT_STEP
   return hipGetLastError();
 }
 
@@ -2246,6 +2311,151 @@ hipError_t reg_penalty(const float* P, long n, const int32_t* reg, int nreg, flo
   const size_t lds = nreg * sizeof(int4) + (SX_NW + 1) * sizeof(float);
   hipLaunchKernelGGL(reg_penalty_k, dim3(grid), dim3(NT), lds, s, P, groups, per, reinterpret_cast<const int4*>(reg),
                      nreg, scratch, tail);
+  return hipGetLastError();
+}
+
+// The L2 norm(s) of the gradient the update rule consumes -- G[i], plus 2 l2 w + l1 sign(w)
+// from P for the elements of a regularized variable, the g opt_step_k forms -- and the Keras
+// clipping scale(s) c / max(norm, c), in a fixed order.  The layout comes as two tables built
+// once by the host: vt, one row (offset, size, l1 bits, l2 bits) per variable, and ct, one
+// (start, row of vt) per chunk; every variable is cut into chunks of GN_CHUNK elements, so a
+// chunk never spans two variables.  Block b takes chunks b, b + grid, ...: a thread adds the
+// squares of its (at most GN_U) 4-element groups, 16-byte loads issued together; a wave
+// shuffle tree, one LDS exchange, one partial per CHUNK.  Variables start on 8-element
+// boundaries and the padding of G behind them is zero (gather_batch clears G and only
+// variables are written; P's padding is zero too), so a chunk's last group may run past the
+// variable's end.  The last block to arrive adds each variable's partials in chunk order (16
+// lanes per variable: lane j takes chunks j, j + 16, ..., then a shuffle tree) or, for the
+// global norm, all of them (reg_penalty_k's order), stores norms and scales and re-arms the
+// counter.  No float atomics, a partition that depends on the layout alone: two launches,
+// and a graph replay against an eager run, give the same bits.  G (and P) are read once.
+// scratch: [nchunk] partials, [1] arrival counter (int, zero before the first launch).
+// out: [nout] norms, [nout] scales; nout = nvar (PERVAR) or 1.
+namespace {
+constexpr int GN_MAX_BLOCKS = 1024, GN_U = 4;
+static_assert(GN_CHUNK == GN_U * NT * 4, "a chunk is one trip of the block");
+__device__ __forceinline__ float clip_scale(float norm, float c) {
+  // exactly 1.0f while norm <= c (0 included); a non-finite norm poisons the update (NaN)
+  const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+  return finite ? c / fmaxf(norm, c) : __uint_as_float(0x7fc00000u);
+}
+template <bool REG, bool PERVAR>
+__global__ __launch_bounds__(NT) void grad_norm_k(const float* __restrict__ G, const float* __restrict__ P,
+                                                  const int4* __restrict__ vt, int nvar,
+                                                  const int2* __restrict__ ct, int nchunk,
+                                                  const int* __restrict__ vfirst, float c, float* scratch,
+                                                  float* out) {
+  __shared__ float wsums[2][SX_NW];  // two sets, used in turn: one barrier per chunk
+  __shared__ int last;
+  const int b = blockIdx.x, t = threadIdx.x, nb = gridDim.x, lane = t & 63, w = t >> 6;
+  int par = 0;
+  for (int ch = b; ch < nchunk; ch += nb, par ^= 1) {
+    float* wsum = wsums[par];
+    const int2 cd = ct[ch];
+    const int4 row = vt[cd.y];
+    const int left = row.x + row.y - cd.x;  // elements of the variable from the chunk's start
+    const int ngrp = ((left < GN_CHUNK ? left : GN_CHUNK) + 3) >> 2;
+    const float l1 = __int_as_float(row.z), l2 = __int_as_float(row.w);
+    const bool reg = REG && (l1 != 0.f || l2 != 0.f);  // uniform over the block
+    float4 g[GN_U];
+#pragma unroll
+    for (int u = 0; u < GN_U; ++u) {
+      const int gi = t + u * NT;
+      g[u] = gi < ngrp ? *reinterpret_cast<const float4*>(G + cd.x + 4 * (long)gi) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (reg) {
+      float4 p[GN_U];
+#pragma unroll
+      for (int u = 0; u < GN_U; ++u) {
+        const int gi = t + u * NT;
+        p[u] = gi < ngrp ? *reinterpret_cast<const float4*>(P + cd.x + 4 * (long)gi) : float4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < GN_U; ++u) {  // opt_step_k's expression: the same g, bit for bit
+        g[u].x += fmaf(2.f * l2, p[u].x, l1 * (float)((p[u].x > 0.f) - (p[u].x < 0.f)));
+        g[u].y += fmaf(2.f * l2, p[u].y, l1 * (float)((p[u].y > 0.f) - (p[u].y < 0.f)));
+        g[u].z += fmaf(2.f * l2, p[u].z, l1 * (float)((p[u].z > 0.f) - (p[u].z < 0.f)));
+        g[u].w += fmaf(2.f * l2, p[u].w, l1 * (float)((p[u].w > 0.f) - (p[u].w < 0.f)));
+      }
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int u = 0; u < GN_U; ++u)
+      acc += (g[u].x * g[u].x + g[u].y * g[u].y) + (g[u].z * g[u].z + g[u].w * g[u].w);
+    acc = sx_wave_sum(acc);
+    if (lane == 0) wsum[w] = acc;
+    __syncthreads();
+    if (t == 0) {
+      float v = wsum[0];
+#pragma unroll
+      for (int u = 1; u < SX_NW; ++u) v += wsum[u];
+      scratch[ch] = v;
+    }
+    // (no second barrier: the next chunk writes the other set, and this set is written
+    // again only behind the next chunk's barrier, which thread 0 reaches after this read)
+  }
+  int* counter = reinterpret_cast<int*>(scratch + nchunk);
+  if (!last_arriver(counter, nb, &last)) return;
+  if constexpr (PERVAR) {
+    // 16 lanes per variable (16 variables at a time: most have one chunk): lane j adds the
+    // variable's chunks j, j + 16, ... in order, then a 4-level shuffle tree inside the group
+    const int grp = t >> 4, gl = t & 15;
+    for (int v0 = 0; v0 < nvar; v0 += NT / 16) {  // the same trip count in every lane
+      const int v = v0 + grp;
+      float a = 0.f;
+      if (v < nvar)
+        for (int k = vfirst[v] + gl; k < vfirst[v + 1]; k += 16) a += scratch[k];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o);
+      if (v < nvar && gl == 0) {
+        const float norm = sqrtf(a);
+        out[v] = norm;
+        out[nvar + v] = clip_scale(norm, c);
+      }
+    }
+  } else {
+    float* wsum = wsums[0];  // (last_arriver's barriers lie behind every read above)
+    float a = 0.f;
+    for (int k = t; k < nchunk; k += NT) a += scratch[k];
+    a = sx_wave_sum(a);
+    if (lane == 0) wsum[w] = a;
+    __syncthreads();
+    if (t == 0) {
+      float v = wsum[0];
+#pragma unroll
+      for (int u = 1; u < SX_NW; ++u) v += wsum[u];
+      const float norm = sqrtf(v);
+      out[0] = norm;
+      out[1] = clip_scale(norm, c);
+    }
+  }
+  if (t == 0) *counter = 0;
+}
+}  // namespace
+
+int grad_norm_blocks(int nchunk) { return nchunk < 1 ? 1 : nchunk > GN_MAX_BLOCKS ? GN_MAX_BLOCKS : nchunk; }
+
+hipError_t grad_norm(const float* G, const float* P, long n, const int32_t* vt, int nvar, const int32_t* ct,
+                     int nchunk, const int32_t* vfirst, int per_variable, float c, float* scratch, float* out,
+                     hipStream_t s) {
+  if (n < 0 || n % 4 || n >= (1L << 31) || nvar < 1 || nchunk < nvar || !(c > 0.f)) return hipErrorInvalidValue;
+  if (G == nullptr || vt == nullptr || ct == nullptr || vfirst == nullptr || scratch == nullptr || out == nullptr)
+    return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(vt)) & 15)
+    return hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(ct) & 7) return hipErrorInvalidValue;
+  const int grid = grad_norm_blocks(nchunk);
+  const int4* v4 = reinterpret_cast<const int4*>(vt);
+  const int2* c2 = reinterpret_cast<const int2*>(ct);
+#define DAMD_GRAD_NORM(REG_, PV_) \
+  hipLaunchKernelGGL((grad_norm_k<REG_, PV_>), dim3(grid), dim3(NT), 0, s, G, P, v4, nvar, c2, nchunk, vfirst, c, \
+                     scratch, out)
+  if (P != nullptr) {
+    if (per_variable) DAMD_GRAD_NORM(true, true); else DAMD_GRAD_NORM(true, false);
+  } else {
+    if (per_variable) DAMD_GRAD_NORM(false, true); else DAMD_GRAD_NORM(false, false);
+  }
+#undef DAMD_GRAD_NORM
   return hipGetLastError();
 }
 

@@ -359,17 +359,27 @@ void register_kernel_ops(py::module_& m) {
           "sgd_step");
   });
   m.def("opt_step", [](U P, U G, U S0, U S1, U S2, U Pb, long n, U ctrl, U tail, int kind, float b1, float b2,
-                       float eps, float rho, float mom, int flag, U s, int book, U reg, int nreg, long lo) {
+                       float eps, float rho, float mom, int flag, U s, int book, U reg, int nreg, long lo, int clip,
+                       float clipc, U scales) {
     damd::OptArgs o{kind, b1, b2, eps, rho, mom, flag};
     check(damd::opt_step(P_<float>(P), P_<const float>(G), P_<float>(S0), P_<float>(S1), P_<float>(S2), P_<u16>(Pb), n,
                          P_<damd::Ctrl>(ctrl), P_<const float>(tail), o, P_<ihipStream_t>(s), book,
-                         P_<const int32_t>(reg), nreg, lo),
+                         P_<const int32_t>(reg), nreg, lo, clip, clipc, P_<const float>(scales)),
           "opt_step");
   }, py::arg("P"), py::arg("G"), py::arg("S0"), py::arg("S1"), py::arg("S2"), py::arg("Pb"), py::arg("n"),
      py::arg("ctrl"), py::arg("tail"), py::arg("kind"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("rho"),
      py::arg("mom"), py::arg("flag"), py::arg("s"), py::arg("book") = 1, py::arg("reg") = 0, py::arg("nreg") = 0,
-     py::arg("lo") = 0);
+     py::arg("lo") = 0, py::arg("clip") = 0, py::arg("clipc") = 0.f, py::arg("scales") = 0);
   m.attr("REG_MAX_ROWS") = damd::REG_MAX_ROWS;
+  m.attr("GN_CHUNK") = damd::GN_CHUNK;
+  m.def("grad_norm_blocks", &damd::grad_norm_blocks);
+  m.def("grad_norm", [](U G, U P, long n, U vt, int nvar, U ct, int nchunk, U vfirst, int per_variable, float c,
+                        U scratch, U out, U s) {
+    check(damd::grad_norm(P_<const float>(G), P_<const float>(P), n, P_<const int32_t>(vt), nvar,
+                          P_<const int32_t>(ct), nchunk, P_<const int32_t>(vfirst), per_variable, c,
+                          P_<float>(scratch), P_<float>(out), P_<ihipStream_t>(s)),
+          "grad_norm");
+  });
   m.def("reg_penalty_blocks", &damd::reg_penalty_blocks);
   m.def("reg_penalty", [](U P, long n, U reg, int nreg, U scratch, U tail, U s) {
     check(damd::reg_penalty(P_<const float>(P), n, P_<const int32_t>(reg), nreg, P_<float>(scratch), P_<float>(tail),

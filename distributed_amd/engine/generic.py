@@ -54,6 +54,8 @@ class GenericEngine(Engine):
         self.step_in_epoch = 0
         self._plan_buckets()
         self._plan_regularizers()
+        # gradient clipping (keras/optimizers.py): read once, when the engine is built
+        self.clip_mode, self.clip_c = model.optimizer.clipping()
 
     def _plan_regularizers(self):
         """Weight penalties (keras/regularizers.py).  L1L2 on a trainable variable: a row
@@ -220,6 +222,11 @@ class GenericEngine(Engine):
         self._tick("allreduce")
         if self.regularized:
             self._add_reg_grad(G[: self.n])
+        if self.clip_mode is not None:
+            # Keras clipping of what the update rule consumes: after the exchange, with dR/dw
+            from ..ops import reference
+
+            reference.clip_grad(G[: self.n], list(zip(self.offs, self.sizes)), self.clip_mode, self.clip_c)
         self.model.optimizer.apply_flat(self.P, G[: self.n])
         self.acc += G[self.n:].double()
         self.step_in_epoch += 1

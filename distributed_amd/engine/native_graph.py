@@ -218,6 +218,21 @@ def regularizers_ok(model):
     return True, ""
 
 
+def clipping_ok(model):
+    """(ok, reason): the optimizer's gradient clipping has a native form.  clipvalue and
+    global_clipnorm always do; clipnorm looks up each element's variable in opt_step's
+    LDS-staged table, which then lists every trainable variable."""
+    mode, c = model.optimizer.clipping()
+    if mode is None:
+        return True, ""
+    if not (np.isfinite(c) and c > 0.0):
+        return False, f"{mode} {c!r} is not a finite number > 0"
+    nvar = len(model.trainable_weights)
+    if mode == "clipnorm" and nvar > H.REG_MAX_ROWS:
+        return False, f"clipnorm: {nvar} variables exceed the table cap {H.REG_MAX_ROWS}"
+    return True, ""
+
+
 def _opt_kernel_slots(opt):
     """(opt_step kind, slot names for S0..S2; '' = unused) of a Keras optimizer."""
     from ..keras import optimizers
@@ -264,6 +279,9 @@ class NativeGraphEngine(Engine):
         if not ok:
             return ok, why
         ok, why = regularizers_ok(model)
+        if not ok:
+            return ok, why
+        ok, why = clipping_ok(model)
         if not ok:
             return ok, why
         return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
@@ -354,6 +372,15 @@ class NativeGraphEngine(Engine):
         rows = reg_rows(self.vars, offs)
         self.reg_tab = H.reg_table(rows, dev) if rows else None
         self.reg_scratch = H.reg_scratch(n, dev) if rows else None
+        # gradient clipping (keras/optimizers.py), constants of the captured step.  clipvalue
+        # lives inside opt_step; the two norm modes run one grad_norm launch over the whole
+        # all-reduced G before the single opt_step: tables, scratch and scales built here
+        self.clip_mode, self.clip_c = model.optimizer.clipping()
+        self.clip_plan = None
+        if self.clip_mode in ("clipnorm", "global_clipnorm"):
+            co = {r[0]: (r[2], r[3]) for r in rows}
+            self.clip_plan = H.clip_plan([(o, sz) + co.get(o, (0.0, 0.0)) for o, sz in zip(offs, self.sizes)], n, dev,
+                                         per_variable=self.clip_mode == "clipnorm")
         # non-trainable (BN moving statistics) live on the device as fp32
         for w in model.non_trainable_weights:
             if w.value.device != dev:
@@ -460,6 +487,13 @@ class NativeGraphEngine(Engine):
         reduce = self.native_comm is not None or self.peer is not None
         self.bucket_opt = (env.get_bool("DAMD_BUCKET_OPT", reduce) and not self.host_collective
                            and len(self._buckets) > 1)
+        if self.bucket_opt and self.clip_plan is not None:
+            # a norm needs the whole gradient before the first update: one opt_step after the
+            # join, whatever DAMD_BUCKET_OPT says (the last buckets' updates no longer overlap
+            # the rest of backward)
+            dlog.info("%s: the optimizer update runs once after all gradient buckets (no per-bucket updates)",
+                      self.clip_mode)
+            self.bucket_opt = False
         if self.bucket_opt and not self._comm_streams:
             self._comm_streams = [torch.cuda.Stream(dev) for _ in self._buckets]
         # convolution weight gradients on a side stream (DAMD_WGRAD_STREAM): a conv's
@@ -1160,11 +1194,22 @@ class NativeGraphEngine(Engine):
             book = int(b["hi"] > self.nparam)
         # (a slot pointer of an unused slot is the dummy: offset, never dereferenced)
         o4 = 4 * lo
+        tab, clip = self.reg_tab, {}
+        if self.clip_mode is not None:
+            clip = dict(clip=H.CLIP_KINDS[self.clip_mode], clipc=self.clip_c)
+        if self.clip_plan is not None:
+            # the norm(s) of the whole all-reduced gradient (+ dR/dw) first: one launch on this
+            # stream, behind every bucket's all-reduce, then the single update
+            assert b is None, "norm clipping updates every parameter in one launch"
+            H.grad_norm(self.G, self.clip_plan, self.clip_c, P=self.P if self.clip_plan.regularized else None)
+            clip["scales"] = self.clip_plan.scales.data_ptr()
+            if self.clip_plan.per_variable:
+                tab = self.clip_plan.vt  # every variable: the row index is the scale index
         self.C.opt_step(self.P.data_ptr() + o4, self.G.data_ptr() + o4, ptr[0] + o4, ptr[1] + o4, ptr[2] + o4,
                         self.Pb.data_ptr() + 2 * lo, max(hi - lo, 0), self.ctrl.data_ptr(),
                         self.G[self.nparam:].data_ptr(), self.opt_kind, *args, H.stream_handle(), book=book,
-                        reg=self.reg_tab.data_ptr() if self.reg_tab is not None else 0,
-                        nreg=self.reg_tab.shape[0] if self.reg_tab is not None else 0, lo=lo)
+                        reg=tab.data_ptr() if tab is not None else 0,
+                        nreg=tab.shape[0] if tab is not None else 0, lo=lo, **clip)
 
     # forward ops
     def _w(self, nd, var):

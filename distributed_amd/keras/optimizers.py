@@ -12,11 +12,33 @@ import math
 import torch
 
 
+CLIP_MODES = ("clipvalue", "clipnorm", "global_clipnorm")
+
+
 class Optimizer:
     def __init__(self, learning_rate=0.001, name="Optimizer", **kw):
         if "lr" in kw:  # Keras alias
             learning_rate = kw.pop("lr")
         self._lr = float(learning_rate)
+        # gradient clipping (tf.keras >= 2.4): at most one of clipvalue / clipnorm /
+        # global_clipnorm, a finite number > 0.  Applied by the engines to the gradient the
+        # update rule consumes (all-reduced mean gradient + weight-regularizer gradient), once
+        # per step after the exchange; read when the engine is built (first fit).
+        given = [(k, kw.pop(k)) for k in CLIP_MODES if kw.get(k) is not None]
+        for k in CLIP_MODES:
+            kw.pop(k, None)
+        if len(given) > 1:
+            raise ValueError(f"at most one of {', '.join(CLIP_MODES)} may be set, got "
+                             f"{', '.join(k for k, _ in given)}")
+        self.clipvalue = self.clipnorm = self.global_clipnorm = None
+        for k, v in given:
+            try:
+                c = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{k} must be a finite number > 0, got {v!r}") from None
+            if not (math.isfinite(c) and c > 0.0):
+                raise ValueError(f"{k} must be a finite number > 0, got {v!r}")
+            setattr(self, k, c)
         self.name = name
         self._iterations = 0
         self._iter_source = None  # callable returning device-side iteration count
@@ -53,8 +75,21 @@ class Optimizer:
     def apply_flat(self, p: torch.Tensor, g: torch.Tensor) -> None:
         raise NotImplementedError
 
+    def clipping(self):
+        """(mode, value) of the configured gradient clipping -- mode one of CLIP_MODES -- or
+        (None, None).  The one place the engines ask."""
+        for k in CLIP_MODES:
+            v = getattr(self, k)
+            if v is not None:
+                return k, float(v)
+        return None, None
+
     def get_config(self):
-        return {"name": self.name, "learning_rate": self._lr}
+        c = {"name": self.name, "learning_rate": self._lr}
+        mode, v = self.clipping()
+        if mode is not None:  # only when set: configs without clipping are what they were
+            c[mode] = v
+        return c
 
 
 class SGD(Optimizer):

@@ -1163,6 +1163,99 @@ def reg_penalty(P, table, scratch, tail=None):
     _C().reg_penalty(_ptr(P), n, _ptr(table), table.shape[0], _ptr(scratch), _ptr(tail), stream_handle())
 
 
+GN_CHUNK = 4096  # layer_ops.h GN_CHUNK: elements per chunk of grad_norm's partition
+CLIP_KINDS = {None: 0, "clipvalue": 1, "clipnorm": 2, "global_clipnorm": 3}  # opt_step's clip argument
+
+
+class ClipPlan:
+    """Device tables and buffers of ``grad_norm`` for one flat-buffer layout (built once: a
+    captured step replays with no allocation).  ``vt`` int32 [nvar, 4]: one row (offset,
+    size, l1 bits, l2 bits) per variable -- also opt_step's table for per-variable clipping;
+    ``ct`` int32 [nchunk, 2]: (start, row) of every chunk; ``vfirst`` int32 [nvar + 1]: each
+    variable's first chunk; ``scratch`` fp32 [nchunk + 1]; ``out`` fp32 [2, nout]: the norms
+    and the scales (``nout`` = nvar per variable, 1 for the global norm)."""
+
+    def __init__(self, rows, n: int, device, per_variable: bool):
+        rows = [(int(r[0]), int(r[1]), float(r[2]) if len(r) > 2 else 0.0, float(r[3]) if len(r) > 3 else 0.0)
+                for r in rows]
+        if rows != sorted(rows) or not rows:
+            raise ValueError("clip_plan: rows must be sorted by offset and not empty")
+        n = int(n)
+        if n % 4 or n >= 2 ** 31:
+            raise ValueError("clip_plan: the flat buffer holds a multiple of 4 floats, below 2^31")
+        end = 0
+        for o, sz, _, _ in rows:
+            if o % 8 or sz <= 0 or o < end or o + sz > n:
+                raise ValueError(f"clip_plan: row (offset {o}, size {sz}) is misaligned, empty, overlaps the "
+                                 f"previous or runs past the buffer ({n})")
+            end = o + sz
+        if per_variable and len(rows) > REG_MAX_ROWS:
+            raise ValueError(f"clip_plan: {len(rows)} variables exceed the table cap {REG_MAX_ROWS}")
+        chunks, first = [], []
+        for r, (o, sz, _, _) in enumerate(rows):
+            first.append(len(chunks))
+            chunks += [(s, r) for s in range(o, o + sz, GN_CHUNK)]
+        first.append(len(chunks))
+        self.n, self.per_variable, self.rows = n, bool(per_variable), rows
+        self.nvar, self.nchunk = len(rows), len(chunks)
+        self.regularized = any(a or b for _, _, a, b in rows)
+        vt = torch.zeros((self.nvar, 4), dtype=torch.int32)
+        vt[:, :2] = torch.tensor([r[:2] for r in rows], dtype=torch.int32)
+        vt[:, 2:] = torch.tensor([r[2:] for r in rows], dtype=torch.float32).view(torch.int32)
+        self.vt = vt.to(device)
+        self.ct = torch.tensor(chunks, dtype=torch.int32).to(device)
+        self.vfirst = torch.tensor(first, dtype=torch.int32).to(device)
+        self.scratch = torch.zeros(self.nchunk + 1, dtype=torch.float32, device=device)
+        self.nout = self.nvar if per_variable else 1
+        self.out = torch.zeros((2, self.nout), dtype=torch.float32, device=device)
+
+    @property
+    def norms(self):
+        return self.out[0]
+
+    @property
+    def scales(self):
+        return self.out[1]
+
+    @property
+    def bytes_read(self):
+        """Bytes of G (and P) one launch loads."""
+        g = sum(4 * ((sz + 3) // 4 * 4) for _, sz, _, _ in self.rows)
+        p = sum(4 * ((sz + 3) // 4 * 4) for _, sz, a, b in self.rows if a or b)
+        return g + p
+
+
+def clip_plan(rows, n, device, per_variable) -> ClipPlan:
+    """:class:`ClipPlan` for variables ``rows`` = (offset, size[, l1, l2]) sorted by offset
+    (offsets multiples of 8, no overlap) in a flat buffer of ``n`` floats."""
+    if _C().GN_CHUNK != GN_CHUNK:
+        raise RuntimeError("ops/hip.py GN_CHUNK does not match the native build")
+    return ClipPlan(rows, n, device, per_variable)
+
+
+def grad_norm(G, plan: ClipPlan, c, P=None):
+    """One launch: the L2 norm(s) of ``G`` over ``plan``'s variables -- with ``P`` (the fp32
+    masters) of ``G + 2 l2 w + l1 sign(w)``, opt_step's regularized gradient -- into
+    ``plan.norms`` and the clipping scales ``c / max(norm, c)`` into ``plan.scales``.  ``G``
+    may be longer than the plan's buffer (a metric tail); the padding between variables
+    must be zero in ``G`` and ``P``."""
+    _chk(G, torch.float32, "G")
+    if G.numel() < plan.n:
+        raise ValueError(f"grad_norm: G holds {G.numel()} floats, the plan covers {plan.n}")
+    if P is not None:
+        _chk(P, torch.float32, "P")
+        if P.numel() < plan.n:
+            raise ValueError(f"grad_norm: P holds {P.numel()} floats, the plan covers {plan.n}")
+    elif plan.regularized:
+        raise ValueError("grad_norm: the plan has regularizer coefficients: pass the masters P")
+    c = float(c)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"grad_norm: c must be a finite number > 0, got {c}")
+    _C().grad_norm(_ptr(G), _ptr(P) if plan.regularized else 0, plan.n, _ptr(plan.vt), plan.nvar, _ptr(plan.ct),
+                   plan.nchunk, _ptr(plan.vfirst), int(plan.per_variable), c, _ptr(plan.scratch), _ptr(plan.out),
+                   stream_handle())
+
+
 def cast_bf16(x, y):
     _C().cast_f32_bf16(_ptr(x), _ptr(y), x.numel(), stream_handle())
 

@@ -101,6 +101,45 @@ def reg_penalty(P, table):
     return r
 
 
+def clip_scale(norm: float, c: float) -> float:
+    """``c / max(norm, c)`` in fp32: exactly 1.0 while ``norm <= c`` (0 included), NaN for a
+    non-finite norm (as tf.clip_by_global_norm: the update is poisoned visibly)."""
+    if not math.isfinite(norm):
+        return float("nan")
+    c32 = torch.tensor(float(c), dtype=torch.float32)
+    return float(c32 / torch.maximum(torch.tensor(float(norm), dtype=torch.float32), c32))
+
+
+@torch.no_grad()
+def clip_grad(g, table, mode, c):
+    """Keras gradient clipping of the flat fp32 gradient ``g`` in place.  ``table``: one
+    ``(offset, size)`` row per variable (further columns are ignored).  ``mode``:
+    ``"clipvalue"``: g <- min(max(g, -c), c) per element; ``"clipnorm"``: per variable
+    g_v <- g_v * c / max(||g_v||, c); ``"global_clipnorm"``: g <- g * c / max(||g||, c) over
+    all rows.  Norms are accumulated in fp64, the scales and products are fp32.  Returns
+    ``(norms, scales)`` as fp64 / fp32 lists -- one entry per row, a single entry for the
+    global mode, empty for clipvalue."""
+    rows = [(int(r[0]), int(r[1])) for r in table]
+    if mode == "clipvalue":
+        for off, size in rows:
+            g[off:off + size].clamp_(-float(c), float(c))
+        return [], []
+    sq = [float(g[off:off + size].double().pow(2).sum()) for off, size in rows]
+    if mode == "global_clipnorm":
+        norm = math.sqrt(sum(sq))
+        s = clip_scale(norm, c)
+        for off, size in rows:
+            g[off:off + size].mul_(s)
+        return [norm], [s]
+    if mode != "clipnorm":
+        raise ValueError(f"clip_grad: mode {mode!r}")
+    norms = [math.sqrt(v) for v in sq]
+    scales = [clip_scale(nv, c) for nv in norms]
+    for (off, size), s in zip(rows, scales):
+        g[off:off + size].mul_(s)
+    return norms, scales
+
+
 def sparse_softmax_xent(logits, labels):
     """Per-sample loss of SparseCategoricalCrossentropy(from_logits=True)."""
     return F.cross_entropy(logits.float(), labels.long(), reduction="none")
