@@ -35,6 +35,26 @@ layer_conv_2d <- function(object = NULL, filters, kernel_size, strides = c(1L, 1
 }
 
 #' @export
+layer_depthwise_conv_2d <- function(object = NULL, kernel_size, strides = c(1L, 1L), padding = "valid",
+                                    depth_multiplier = 1L, activation = NULL, use_bias = TRUE, input_shape = NULL,
+                                    name = NULL, ...) {
+  .r()$layer_depthwise_conv_2d(object, kernel_size = .ints(kernel_size), strides = .ints(strides),
+                               padding = padding, depth_multiplier = .int(depth_multiplier),
+                               activation = activation, use_bias = use_bias, input_shape = .ints(input_shape),
+                               name = name, ...)
+}
+
+#' @export
+layer_separable_conv_2d <- function(object = NULL, filters, kernel_size, strides = c(1L, 1L), padding = "valid",
+                                    depth_multiplier = 1L, activation = NULL, use_bias = TRUE, input_shape = NULL,
+                                    name = NULL, ...) {
+  .r()$layer_separable_conv_2d(object, filters = .int(filters), kernel_size = .ints(kernel_size),
+                               strides = .ints(strides), padding = padding,
+                               depth_multiplier = .int(depth_multiplier), activation = activation,
+                               use_bias = use_bias, input_shape = .ints(input_shape), name = name, ...)
+}
+
+#' @export
 layer_max_pooling_2d <- function(object = NULL, pool_size = c(2L, 2L), strides = NULL, padding = "valid",
                                  name = NULL) {
   .r()$layer_max_pooling_2d(object, pool_size = .ints(pool_size), strides = .ints(strides), padding = padding,

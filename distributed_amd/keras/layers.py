@@ -110,7 +110,7 @@ class KerasTensor:
 
 # accepted for Keras compatibility and not applied: a non-None value warns
 _UNSUPPORTED_KW = ("activity_regularizer", "kernel_constraint", "bias_constraint", "gamma_constraint",
-                   "beta_constraint")
+                   "beta_constraint", "depthwise_constraint", "pointwise_constraint")
 
 
 class Layer:
@@ -286,6 +286,118 @@ class Conv2D(Layer):
                  kernel_regularizer=_reg.serialize(self.kernel_regularizer),
                  bias_regularizer=_reg.serialize(self.bias_regularizer), activity_regularizer=None,
                  kernel_constraint=None, bias_constraint=None)
+        return c
+
+
+class DepthwiseConv2D(Layer):
+    """Keras DepthwiseConv2D: every input channel filtered on its own by ``depth_multiplier``
+    kernels.  ``depthwise_kernel`` is ``(kh, kw, Cin, depth_multiplier)``; output channel
+    ``c * depth_multiplier + m`` is input channel ``c`` under ``depthwise_kernel[:, :, c, m]``."""
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, depthwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(**kw)
+        self.depthwise_regularizer = _reg.get(depthwise_regularizer)
+        self.bias_regularizer = _reg.get(bias_regularizer)
+        if data_format not in (None, "channels_last"):
+            raise ValueError("only channels_last (NHWC) is supported, as in the reference")
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        self.padding = padding.lower()
+        self.depth_multiplier = int(depth_multiplier)
+        if self.depth_multiplier < 1:
+            raise ValueError(f"depth_multiplier must be >= 1, got {depth_multiplier}")
+        self.dilation_rate = _pair(dilation_rate)
+        self.activation = _act.get(activation)
+        self.use_bias = use_bias
+        self.depthwise_initializer = _init.get(depthwise_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        if self._batch_input_shape is not None:
+            self._maybe_build(self._batch_input_shape)
+
+    def _out_channels(self, cin):
+        return cin * self.depth_multiplier
+
+    def _build_depthwise(self, cin):
+        self.depthwise_kernel = self.add_weight("depthwise_kernel", self.kernel_size + (cin, self.depth_multiplier),
+                                                self.depthwise_initializer, regularizer=self.depthwise_regularizer)
+
+    def build(self, input_shape):
+        cin = int(input_shape[-1])
+        self._build_depthwise(cin)
+        self.bias = (self.add_weight("bias", (self._out_channels(cin),), self.bias_initializer,
+                                     regularizer=self.bias_regularizer) if self.use_bias else None)
+
+    def compute_output_shape(self, s):
+        n, h, w, c = s
+        out = []
+        for size, k, st, d in zip((h, w), self.kernel_size, self.strides, self.dilation_rate):
+            eff = (k - 1) * d + 1
+            out.append(None if size is None else
+                       (math.ceil(size / st) if self.padding == "same" else (size - eff) // st + 1))
+        return (n, out[0], out[1], self._out_channels(c))
+
+    def call(self, x, training=False):
+        y = ops.depthwise_conv2d(x, self.depthwise_kernel.value, self.bias.value if self.bias is not None else None,
+                                 self.strides, self.padding, self.dilation_rate)
+        return self.activation(y)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(kernel_size=list(self.kernel_size), strides=list(self.strides), padding=self.padding,
+                 data_format="channels_last", dilation_rate=list(self.dilation_rate),
+                 depth_multiplier=self.depth_multiplier, activation=_act.serialize(self.activation),
+                 use_bias=self.use_bias, depthwise_initializer=_init.serialize(self.depthwise_initializer),
+                 bias_initializer=_init.serialize(self.bias_initializer),
+                 depthwise_regularizer=_reg.serialize(self.depthwise_regularizer),
+                 bias_regularizer=_reg.serialize(self.bias_regularizer), activity_regularizer=None,
+                 depthwise_constraint=None, bias_constraint=None)
+        return c
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """Keras SeparableConv2D: a depthwise convolution (no bias, no activation) followed by a
+    1x1 convolution over ``pointwise_kernel`` ``(1, 1, Cin * depth_multiplier, filters)``; bias
+    and activation come after the pointwise half.  Weights in Keras order: depthwise_kernel,
+    pointwise_kernel, bias."""
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None,
+                 dilation_rate=(1, 1), depth_multiplier=1, activation=None, use_bias=True,
+                 depthwise_initializer="glorot_uniform", pointwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, pointwise_regularizer=None,
+                 bias_regularizer=None, **kw):
+        self.filters = int(filters)
+        self.pointwise_initializer = _init.get(pointwise_initializer)
+        self.pointwise_regularizer = _reg.get(pointwise_regularizer)
+        super().__init__(kernel_size, strides=strides, padding=padding, depth_multiplier=depth_multiplier,
+                         data_format=data_format, dilation_rate=dilation_rate, activation=activation,
+                         use_bias=use_bias, depthwise_initializer=depthwise_initializer,
+                         bias_initializer=bias_initializer, depthwise_regularizer=depthwise_regularizer,
+                         bias_regularizer=bias_regularizer, **kw)
+
+    def _out_channels(self, cin):
+        return self.filters
+
+    def build(self, input_shape):
+        cin = int(input_shape[-1])
+        self._build_depthwise(cin)
+        self.pointwise_kernel = self.add_weight("pointwise_kernel",
+                                                (1, 1, cin * self.depth_multiplier, self.filters),
+                                                self.pointwise_initializer, regularizer=self.pointwise_regularizer)
+        self.bias = (self.add_weight("bias", (self.filters,), self.bias_initializer,
+                                     regularizer=self.bias_regularizer) if self.use_bias else None)
+
+    def call(self, x, training=False):
+        y = ops.depthwise_conv2d(x, self.depthwise_kernel.value, None, self.strides, self.padding,
+                                 self.dilation_rate)
+        y = ops.conv2d(y, self.pointwise_kernel.value, self.bias.value if self.bias is not None else None)
+        return self.activation(y)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(filters=self.filters, pointwise_initializer=_init.serialize(self.pointwise_initializer),
+                 pointwise_regularizer=_reg.serialize(self.pointwise_regularizer), pointwise_constraint=None)
         return c
 
 
@@ -537,5 +649,5 @@ def add(inputs):
 
 
 LAYER_CLASSES = {c.__name__: c for c in (
-    InputLayer, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
+    InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Dense, Activation, ReLU, Softmax, Dropout, ZeroPadding2D, BatchNormalization, Add)}

@@ -9,6 +9,7 @@ dispatch layer between the two.
 from . import reference  # noqa: F401
 from .reference import (  # noqa: F401
     conv2d,
+    depthwise_conv2d,
     dense,
     maxpool2d,
     avgpool2d,

@@ -34,6 +34,23 @@ def conv2d(x, w, b=None, strides=(1, 1), padding="valid", dilation=(1, 1)):
     return y.permute(0, 2, 3, 1)
 
 
+def depthwise_conv2d(x, w, b=None, strides=(1, 1), padding="valid", dilation=(1, 1)):
+    """x [N,H,W,Cin], w [kh,kw,Cin,mult] -> [N,Ho,Wo,Cin*mult]: output channel c*mult + m is
+    input channel c filtered by w[:, :, c, m] (TF's order: a grouped conv with groups = Cin
+    over the kernel reshaped to [Cin*mult, 1, kh, kw])."""
+    kh, kw, cin, mult = w.shape
+    xc = x.permute(0, 3, 1, 2)
+    wc = w.permute(2, 3, 0, 1).reshape(cin * mult, 1, kh, kw)
+    if padding == "same":
+        pt, pb = _same_pad(x.shape[1], kh, strides[0], dilation[0])
+        pl, pr = _same_pad(x.shape[2], kw, strides[1], dilation[1])
+        xc = F.pad(xc, (pl, pr, pt, pb))
+    elif padding != "valid":
+        raise ValueError(f"padding {padding!r}")
+    y = F.conv2d(xc, wc, b, stride=tuple(strides), dilation=tuple(dilation), groups=cin)
+    return y.permute(0, 2, 3, 1)
+
+
 def maxpool2d(x, pool=(2, 2), strides=None, padding="valid"):
     strides = strides or pool
     xc = x.permute(0, 3, 1, 2)

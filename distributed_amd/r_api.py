@@ -92,6 +92,24 @@ def layer_conv_2d(object=None, filters=None, kernel_size=None, strides=(1, 1), p
     return _add(object, _keras.layers.Conv2D(int(filters), kernel_size, **kwargs))
 
 
+def layer_depthwise_conv_2d(object=None, kernel_size=None, strides=(1, 1), padding="valid", depth_multiplier=1,
+                            activation=None, use_bias=True, input_shape=None, name=None, **kw):
+    kwargs = dict(strides=strides, padding=padding, depth_multiplier=int(depth_multiplier), activation=activation,
+                  use_bias=use_bias, name=name, **kw)
+    if input_shape is not None:
+        kwargs["input_shape"] = _shape(input_shape)
+    return _add(object, _keras.layers.DepthwiseConv2D(kernel_size, **kwargs))
+
+
+def layer_separable_conv_2d(object=None, filters=None, kernel_size=None, strides=(1, 1), padding="valid",
+                            depth_multiplier=1, activation=None, use_bias=True, input_shape=None, name=None, **kw):
+    kwargs = dict(strides=strides, padding=padding, depth_multiplier=int(depth_multiplier), activation=activation,
+                  use_bias=use_bias, name=name, **kw)
+    if input_shape is not None:
+        kwargs["input_shape"] = _shape(input_shape)
+    return _add(object, _keras.layers.SeparableConv2D(int(filters), kernel_size, **kwargs))
+
+
 def layer_max_pooling_2d(object=None, pool_size=(2, 2), strides=None, padding="valid", name=None):
     return _add(object, _keras.layers.MaxPooling2D(pool_size, strides, padding, name=name))
 
