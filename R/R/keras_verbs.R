@@ -103,6 +103,42 @@ regularizer_l2 <- function(l = 0.01) .r()$regularizer_l2(l = l)
 #' @export
 regularizer_l1_l2 <- function(l1 = 0.01, l2 = 0.01) .r()$regularizer_l1_l2(l1 = l1, l2 = l2)
 
+# Learning-rate schedules, e.g.
+# optimizer_sgd(learning_rate = learning_rate_schedule_cosine_decay(0.1, 1000, warmup_target = 0.4, warmup_steps = 50))
+#' @export
+learning_rate_schedule_exponential_decay <- function(initial_learning_rate, decay_steps, decay_rate,
+                                                     staircase = FALSE, ...) {
+  .r()$learning_rate_schedule_exponential_decay(initial_learning_rate, decay_steps, decay_rate,
+                                                staircase = staircase, ...)
+}
+
+#' @export
+learning_rate_schedule_inverse_time_decay <- function(initial_learning_rate, decay_steps, decay_rate,
+                                                      staircase = FALSE, ...) {
+  .r()$learning_rate_schedule_inverse_time_decay(initial_learning_rate, decay_steps, decay_rate,
+                                                 staircase = staircase, ...)
+}
+
+#' @export
+learning_rate_schedule_polynomial_decay <- function(initial_learning_rate, decay_steps, end_learning_rate = 1e-4,
+                                                    power = 1, cycle = FALSE, ...) {
+  .r()$learning_rate_schedule_polynomial_decay(initial_learning_rate, decay_steps,
+                                               end_learning_rate = end_learning_rate, power = power,
+                                               cycle = cycle, ...)
+}
+
+#' @export
+learning_rate_schedule_piecewise_constant_decay <- function(boundaries, values, ...) {
+  .r()$learning_rate_schedule_piecewise_constant_decay(as.list(boundaries), as.list(values), ...)
+}
+
+#' @export
+learning_rate_schedule_cosine_decay <- function(initial_learning_rate, decay_steps, alpha = 0,
+                                                warmup_target = NULL, warmup_steps = 0, ...) {
+  .r()$learning_rate_schedule_cosine_decay(initial_learning_rate, decay_steps, alpha = alpha,
+                                           warmup_target = warmup_target, warmup_steps = warmup_steps, ...)
+}
+
 #' @export
 compile <- function(object, optimizer = NULL, loss = NULL, metrics = NULL, ...) {
   invisible(.tag(.r()$compile(object, optimizer = optimizer, loss = loss, metrics = metrics, ...)))

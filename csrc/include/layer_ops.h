@@ -187,10 +187,41 @@ struct OptArgs {
 // there is no regularizer; nreg = the number of variables <= REG_MAX_ROWS) and row is the
 // element's row -- the index grad_norm stores its scales under.  scales: grad_norm's output.
 // clip == 0 is the kernel without any clipping code.
+//
+// sched (optional): a Keras learning-rate schedule (keras/schedules.py) evaluated on the
+// device.  Every thread computes lr = f(ctrl->cur3 - 1) -- the optimizer's iterations before
+// this update -- once before its element loop, in fp32, with all step logic (staircase
+// floor, cycle ceil, clamps, boundary search, warm-up branch) in integer arithmetic; the
+// update rules (Adam's lr_t included) use it instead of ctrl->lr, and the bookkeeping launch
+// stores it into ctrl->lr for the host to read (under a schedule no launch reads that
+// field).  The descriptor is LR_WORDS 32-bit words in HOST memory, 16-byte aligned (build it
+// with ops/hip.py lr_table); opt_step checks it and hands it to the kernel by value, as a
+// kernel argument: the words arrive in scalar registers with the other arguments -- no
+// table load, provably wave-uniform -- and are a constant of a captured step, like clipc.
+// sched == nullptr is the kernel without any schedule code, reading ctrl->lr.
+constexpr int LR_MAX_BOUNDS = 16;  // boundaries of a PiecewiseConstantDecay
+constexpr int LR_MAX_STEPS = 1 << 24;  // decay_steps / warmup_steps: exact as a float
+enum : int { LR_EXPONENTIAL = 1, LR_INVERSE_TIME = 2, LR_POLYNOMIAL = 3, LR_PIECEWISE = 4, LR_COSINE = 5 };
+struct alignas(16) LrSched {
+  int32_t kind;          // 0  LR_*
+  int32_t flags;         // 1  bit 0: staircase (1, 2) / cycle (3) / warm-up (5)
+  int32_t decay_steps;   // 2  in [1, LR_MAX_STEPS] (kind 4: unused)
+  int32_t warmup_steps;  // 3  in [0, LR_MAX_STEPS] (kind 5 with warm-up)
+  float init;            // 4  initial_learning_rate
+  float a;               // 5  decay_rate (1, 2) / end_learning_rate (3) / alpha (5)
+  float b;               // 6  power (3) / warmup_target (5)
+  int32_t nbounds;       // 7  kind 4: boundaries in use, <= LR_MAX_BOUNDS
+  int32_t bounds[LR_MAX_BOUNDS];     // 8   strictly increasing
+  float values[LR_MAX_BOUNDS + 1];   // 24  nbounds + 1 in use
+  int32_t pad[3];
+};
+constexpr int LR_WORDS = sizeof(LrSched) / 4;
+static_assert(sizeof(LrSched) == 44 * 4, "ops/hip.py lr_table lays these words out");
 constexpr int REG_MAX_ROWS = 2048;  // 32 KB of LDS per block
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
                     const float* tail, const OptArgs& o, hipStream_t s, int book = 1, const int32_t* reg = nullptr,
-                    int nreg = 0, long lo = 0, int clip = 0, float clipc = 0.f, const float* scales = nullptr);
+                    int nreg = 0, long lo = 0, int clip = 0, float clipc = 0.f, const float* scales = nullptr,
+                    const LrSched* sched = nullptr);
 // The L2 norm of the gradient opt_step consumes -- G, plus 2 l2 w + l1 sign(w) from the
 // masters P where vt has coefficients (P == nullptr: G alone, P is not read) -- per variable
 // (per_variable != 0) or over all variables, and the clipping scale c / max(norm, c): exactly

@@ -2034,9 +2034,11 @@ __global__ __launch_bounds__(NT) void unpad_add_k(const float* src, int R, int C
 }  // namespace
 
 // Keras optimizer_v2 update rules on the flat fp32 master buffer (+ bf16 shadow): the
-// native-engine counterpart of keras/optimizers.py apply_flat.  lr from ctrl (a schedule
-// needs no re-capture); Adam's step t = ctrl->cur3, written by gather_batch at the start
-// of the step (no block of this kernel reads a ctrl field this kernel writes).
+// native-engine counterpart of keras/optimizers.py apply_flat.  lr from ctrl (a new rate
+// needs no re-capture) or from a schedule descriptor (SCHED, lr_eval below); Adam's step
+// t = ctrl->cur3, written by gather_batch at the start of the step (no block of this kernel
+// reads a ctrl field this kernel writes: under SCHED the bookkeeping thread stores lr, which
+// no launch then reads).
 //
 // Weight regularizers (REG): a segment table, one row (offset, size, l1 bits, l2 bits) per
 // regularized variable, sorted by offset; offsets index the engine's whole flat buffer and
@@ -2085,20 +2087,66 @@ __device__ __forceinline__ int reg_find_row(const int4* tab, int nreg, long i) {
   return (a > 0 && i < (long)tab[a - 1].x + tab[a - 1].y) ? a - 1 : -1;
 }
 
-template <bool REG, int CLIP>
+// A Keras learning-rate schedule (SCHED; keras/schedules.py) at `step`, the optimizer's
+// iterations before this update: fp32 values, integer step logic -- p, s, d, the boundary
+// search and the warm-up branch are exact, so a boundary step never lands on the wrong side
+// through rounding.  q is a kernel argument (scalar registers): every index below is a
+// compile-time constant after unrolling, every branch wave-uniform.  ops/reference.py
+// lr_schedule32 performs the same operations in numpy.float32.
+__device__ __forceinline__ float lr_eval(const LrSched& q, int step) {
+  const int ds = q.decay_steps;
+  switch (q.kind) {
+    case LR_EXPONENTIAL:
+    case LR_INVERSE_TIME: {
+      const float p = (q.flags & 1) ? (float)(step / ds) : (float)step / (float)ds;
+      return q.kind == LR_EXPONENTIAL ? q.init * powf(q.a, p) : q.init / (1.f + q.a * p);
+    }
+    case LR_POLYNOMIAL: {
+      long s = step < ds ? step : ds, d = ds;
+      if (q.flags & 1) {
+        const long m = ((long)step + ds - 1) / ds;  // ceil(step / decay_steps)
+        s = step;
+        d = (long)ds * (m > 1 ? m : 1);
+      }
+      return (q.init - q.a) * powf(1.f - (float)s / (float)d, q.b) + q.a;
+    }
+    case LR_PIECEWISE: {
+      float v = q.values[0];
+#pragma unroll
+      for (int i = 0; i < LR_MAX_BOUNDS; ++i)
+        if (i < q.nbounds && step > q.bounds[i]) v = q.values[i + 1];
+      return v;
+    }
+    default: {  // LR_COSINE
+      float init = q.init;
+      if (q.flags & 1) {
+        if (step < q.warmup_steps) return q.init + (q.b - q.init) * (float)step / (float)q.warmup_steps;
+        init = q.b;
+        step -= q.warmup_steps;
+      }
+      const int s = step < ds ? step : ds;
+      const float c = cosf(3.14159265358979323846f * (float)s / (float)ds);
+      return init * ((1.f - q.a) * 0.5f * (1.f + c) + q.a);
+    }
+  }
+}
+
+template <bool REG, int CLIP, bool SCHED>
 __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const float* __restrict__ G,
                                                  float* __restrict__ S0, float* __restrict__ S1,
                                                  float* __restrict__ S2, uint16_t* __restrict__ Pb, long n,
                                                  Ctrl* ctrl, const float* tail, OptArgs o, int book,
                                                  const int4* reg, int nreg, long lo, float clipc,
-                                                 const float* __restrict__ scales) {
+                                                 const float* __restrict__ scales, LrSched sched) {
   extern __shared__ __attribute__((aligned(16))) int4 reg_lds[];
   RegSeg seg{1, 0, 0.f, 0.f};
   if constexpr (REG || CLIP == CLIP_VAR) reg_stage(reg_lds, reg, nreg);
   float gscale = 1.f;  // CLIP_GLOBAL: the one scale; CLIP_VAR: the scale of seg's row
   if constexpr (CLIP == CLIP_GLOBAL) gscale = scales[0];
-  const float lr = ctrl->lr;
   const int t = ctrl->cur3;
+  float lr;
+  if constexpr (SCHED) lr = lr_eval(sched, t > 1 ? t - 1 : 0);
+  else lr = ctrl->lr;
   float lr_t = lr;
   if (o.kind == 1) lr_t = lr * sqrtf(1.f - powf(o.b2, (float)t)) / (1.f - powf(o.b1, (float)t));
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
@@ -2178,6 +2226,7 @@ __global__ __launch_bounds__(NT) void opt_step_k(float* __restrict__ P, const fl
     if (ctrl->wrap > 0 && c >= ctrl->wrap) c = 0;
     ctrl->cursor = c;
     ctrl->iterations = t;
+    if constexpr (SCHED) ctrl->lr = lr;  // the rate this step used, for the host to read
   }
 }
 
@@ -2185,16 +2234,35 @@ namespace {
 template <bool REG, int CLIP>
 void opt_step_launch(int grid, size_t lds, hipStream_t s, float* P, const float* G, float* S0, float* S1, float* S2,
                      uint16_t* Pb, long n, Ctrl* ctrl, const float* tail, const OptArgs& o, int book,
-                     const int32_t* reg, int nreg, long lo, float clipc, const float* scales) {
-  hipLaunchKernelGGL((opt_step_k<REG, CLIP>), dim3(grid), dim3(NT), lds, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o,
-                     book, reinterpret_cast<const int4*>(reg), nreg, lo, clipc, scales);
+                     const int32_t* reg, int nreg, long lo, float clipc, const float* scales,
+                     const LrSched* sched) {
+  if (sched != nullptr)
+    hipLaunchKernelGGL((opt_step_k<REG, CLIP, true>), dim3(grid), dim3(NT), lds, s, P, G, S0, S1, S2, Pb, n, ctrl,
+                       tail, o, book, reinterpret_cast<const int4*>(reg), nreg, lo, clipc, scales, *sched);
+  else
+    hipLaunchKernelGGL((opt_step_k<REG, CLIP, false>), dim3(grid), dim3(NT), lds, s, P, G, S0, S1, S2, Pb, n, ctrl,
+                       tail, o, book, reinterpret_cast<const int4*>(reg), nreg, lo, clipc, scales, LrSched{});
 }
 }  // namespace
 
 hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, uint16_t* Pb, long n, Ctrl* ctrl,
                     const float* tail, const OptArgs& o, hipStream_t s, int book, const int32_t* reg, int nreg,
-                    long lo, int clip, float clipc, const float* scales) {
+                    long lo, int clip, float clipc, const float* scales, const LrSched* sched) {
   if (o.kind < 0 || o.kind > 2 || n < 0) return hipErrorInvalidValue;
+  if (sched != nullptr) {
+    if (reinterpret_cast<uintptr_t>(sched) & 15) return hipErrorInvalidValue;
+    const LrSched& q = *sched;
+    if (q.kind < LR_EXPONENTIAL || q.kind > LR_COSINE) return hipErrorInvalidValue;
+    if (q.kind == LR_PIECEWISE) {
+      if (q.nbounds < 0 || q.nbounds > LR_MAX_BOUNDS) return hipErrorInvalidValue;
+      for (int i = 1; i < q.nbounds; ++i)
+        if (q.bounds[i] <= q.bounds[i - 1]) return hipErrorInvalidValue;
+    } else if (q.decay_steps < 1 || q.decay_steps > LR_MAX_STEPS) {
+      return hipErrorInvalidValue;
+    }
+    if (q.kind == LR_COSINE && (q.flags & 1) && (q.warmup_steps < 0 || q.warmup_steps > LR_MAX_STEPS))
+      return hipErrorInvalidValue;
+  }
   if (clip < CLIP_NONE || clip > CLIP_GLOBAL) return hipErrorInvalidValue;
   if (clip == CLIP_VALUE && !(clipc > 0.f)) return hipErrorInvalidValue;
   if ((clip == CLIP_VAR || clip == CLIP_GLOBAL) && scales == nullptr) return hipErrorInvalidValue;
@@ -2205,7 +2273,8 @@ hipError_t opt_step(float* P, const float* G, float* S0, float* S1, float* S2, u
     return hipErrorInvalidValue;
   const size_t lds = table ? nreg * sizeof(int4) : 0;
 #define DAMD_OPT_STEP(REG_, CLIP_) \
-  opt_step_launch<REG_, CLIP_>(grid, lds, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book, reg, nreg, lo, clipc, scales)
+  opt_step_launch<REG_, CLIP_>(grid, lds, s, P, G, S0, S1, S2, Pb, n, ctrl, tail, o, book, reg, nreg, lo, clipc, \
+                               scales, sched)
   if (!table) {
     switch (clip) {
       case CLIP_NONE: DAMD_OPT_STEP(false, CLIP_NONE); break;

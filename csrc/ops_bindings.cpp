@@ -360,17 +360,22 @@ void register_kernel_ops(py::module_& m) {
   });
   m.def("opt_step", [](U P, U G, U S0, U S1, U S2, U Pb, long n, U ctrl, U tail, int kind, float b1, float b2,
                        float eps, float rho, float mom, int flag, U s, int book, U reg, int nreg, long lo, int clip,
-                       float clipc, U scales) {
+                       float clipc, U scales, U lr) {
     damd::OptArgs o{kind, b1, b2, eps, rho, mom, flag};
     check(damd::opt_step(P_<float>(P), P_<const float>(G), P_<float>(S0), P_<float>(S1), P_<float>(S2), P_<u16>(Pb), n,
                          P_<damd::Ctrl>(ctrl), P_<const float>(tail), o, P_<ihipStream_t>(s), book,
-                         P_<const int32_t>(reg), nreg, lo, clip, clipc, P_<const float>(scales)),
+                         P_<const int32_t>(reg), nreg, lo, clip, clipc, P_<const float>(scales),
+                         P_<const damd::LrSched>(lr)),
           "opt_step");
   }, py::arg("P"), py::arg("G"), py::arg("S0"), py::arg("S1"), py::arg("S2"), py::arg("Pb"), py::arg("n"),
      py::arg("ctrl"), py::arg("tail"), py::arg("kind"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("rho"),
      py::arg("mom"), py::arg("flag"), py::arg("s"), py::arg("book") = 1, py::arg("reg") = 0, py::arg("nreg") = 0,
-     py::arg("lo") = 0, py::arg("clip") = 0, py::arg("clipc") = 0.f, py::arg("scales") = 0);
+     py::arg("lo") = 0, py::arg("clip") = 0, py::arg("clipc") = 0.f, py::arg("scales") = 0,
+     py::arg("lr") = 0);  // lr: a HOST pointer to LR_WORDS words (ops/hip.py lr_table), read before returning
   m.attr("REG_MAX_ROWS") = damd::REG_MAX_ROWS;
+  m.attr("LR_MAX_BOUNDS") = damd::LR_MAX_BOUNDS;
+  m.attr("LR_MAX_STEPS") = damd::LR_MAX_STEPS;
+  m.attr("LR_WORDS") = damd::LR_WORDS;
   m.attr("GN_CHUNK") = damd::GN_CHUNK;
   m.def("grad_norm_blocks", &damd::grad_norm_blocks);
   m.def("grad_norm", [](U G, U P, long n, U vt, int nvar, U ct, int nchunk, U vfirst, int per_variable, float c,

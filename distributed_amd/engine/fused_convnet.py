@@ -72,6 +72,8 @@ class FusedConvNetEngine(Engine):
             return False, "regularizers"
         if model.optimizer.clipping()[0] is not None:  # the native graph engine's grad_norm / opt_step
             return False, "gradient clipping"
+        if not isinstance(model.optimizer.learning_rate, (int, float)):  # the native graph engine's opt_step
+            return False, "learning-rate schedule"
         c, p, f, d1, d2 = ls
         if not (isinstance(c, L.Conv2D) and c.filters == 32 and c.kernel_size == (3, 3) and c.strides == (1, 1)
                 and c.padding == "valid" and c.dilation_rate == (1, 1) and c.use_bias

@@ -44,6 +44,12 @@ class GenericEngine(Engine):
         self.G = torch.zeros(self.n + self.ntail, dtype=torch.float32, device=dev)
         self.acc = torch.zeros(self.ntail, dtype=torch.float64, device=dev)
         model.optimizer.ensure_slots(self.n, dev)
+        opt = model.optimizer
+        if opt._iter_source is not None:
+            # a native engine counted the iterations on its device: apply_flat counts on the
+            # host, and a learning-rate schedule (or Adam's t) continues from that count
+            opt._iterations = int(opt.iterations)
+            opt._iter_source = None
         # mirrored variables: replicas start from worker 0's values
         if self.world > 1:
             comm = strategy.communicator

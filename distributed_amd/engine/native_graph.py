@@ -29,6 +29,7 @@ from __future__ import annotations
 import gc
 import math
 import struct
+import weakref
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -233,6 +234,25 @@ def clipping_ok(model):
     return True, ""
 
 
+def _schedule_of(opt):
+    """The optimizer's learning-rate schedule, or None for a plain number."""
+    from ..keras.schedules import LearningRateSchedule
+
+    lr = opt.learning_rate
+    return lr if isinstance(lr, LearningRateSchedule) else None
+
+
+def schedule_ok(model):
+    """(ok, reason): the optimizer's learning rate has a native form.  A number always does
+    (ctrl's lr); a schedule when opt_step's descriptor holds it (ops/hip.py lr_schedule_ok):
+    one of the five keras/schedules.py classes with integral step counts in range, at most
+    H.LR_MAX_BOUNDS integer boundaries and finite parameters."""
+    sched = _schedule_of(model.optimizer)
+    if sched is None:
+        return True, ""
+    return H.lr_schedule_ok(sched)
+
+
 def _opt_kernel_slots(opt):
     """(opt_step kind, slot names for S0..S2; '' = unused) of a Keras optimizer."""
     from ..keras import optimizers
@@ -282,6 +302,9 @@ class NativeGraphEngine(Engine):
         if not ok:
             return ok, why
         ok, why = clipping_ok(model)
+        if not ok:
+            return ok, why
+        ok, why = schedule_ok(model)
         if not ok:
             return ok, why
         return loss_head_ok(model, output_head(_layer_graph(model)[0])[0])
@@ -381,6 +404,11 @@ class NativeGraphEngine(Engine):
             co = {r[0]: (r[2], r[3]) for r in rows}
             self.clip_plan = H.clip_plan([(o, sz) + co.get(o, (0.0, 0.0)) for o, sz in zip(offs, self.sizes)], n, dev,
                                          per_variable=self.clip_mode == "clipnorm")
+        # learning-rate schedule (keras/schedules.py): opt_step's descriptor, a constant of the
+        # captured step built once (None: a plain rate, read from ctrl).  The optimizer tells
+        # the engine when a schedule is assigned or removed (lr_changed).
+        self._build_lr_table()
+        model.optimizer._lr_listener = weakref.WeakMethod(self.lr_changed)
         # non-trainable (BN moving statistics) live on the device as fp32
         for w in model.non_trainable_weights:
             if w.value.device != dev:
@@ -1023,10 +1051,22 @@ class NativeGraphEngine(Engine):
         return tmp, finish
 
     # --- hyper-parameters / ctrl -------------------------------------------------------------
+    def _build_lr_table(self):
+        self.lr_sched = _schedule_of(self.model.optimizer)
+        self.lr_tab = H.lr_table(self.lr_sched, self.device) if self.lr_sched is not None else None
+
+    def _host_lr(self):
+        """The rate for ctrl's lr: the number, or the schedule at the current iterations
+        (what the next step's kernel will compute and store there itself)."""
+        opt = self.model.optimizer
+        if self.lr_sched is not None:
+            return float(self.lr_sched(int(opt.iterations)))
+        return opt.learning_rate
+
     def _write_hparams(self):
         opt = self.model.optimizer
         c = self.ctrl.cpu()
-        c[C_LR] = _f2i(opt.learning_rate)
+        c[C_LR] = _f2i(self._host_lr())
         c[C_MOM] = _f2i(getattr(opt, "momentum", 0.0))
         c[C_NEST] = int(getattr(opt, "nesterov", False))
         c[C_ROW0] = self.rank * self.per_replica
@@ -1046,7 +1086,19 @@ class NativeGraphEngine(Engine):
         return int(self.ctrl[C_IT].item())
 
     def lr_changed(self):
-        self._ctrl_write({C_LR: _f2i(self.model.optimizer.learning_rate)})
+        sched = _schedule_of(self.model.optimizer)
+        if sched is not self.lr_sched:
+            # a schedule came, went or was replaced: the descriptor is baked into the captured
+            # step's optimizer launches
+            torch.cuda.synchronize(self.device)
+            self.graph = None
+            if not schedule_ok(self.model)[0]:
+                # no native form: the next fit selects an engine again, and the fallback
+                # warning (or DAMD_STRICT_NATIVE's error) says why
+                self.model._engine_key = None
+                return
+            self._build_lr_table()
+        self._ctrl_write({C_LR: _f2i(self._host_lr())})
 
     def _load_momentum(self):
         # optimizer slots are dense over the unpadded weights (Keras order)
@@ -1105,7 +1157,7 @@ class NativeGraphEngine(Engine):
         torch.index_select(self.feed.y, 0, perm, out=self.y_ep)
         opt = self.model.optimizer
         self._ctrl_write({C_CUR: 0, C_AL: 0, C_AC: 0, C_AN: 0, C_WRAP: int(wrap_steps),
-                          C_LR: _f2i(opt.learning_rate), C_MOM: _f2i(getattr(opt, "momentum", 0.0)),
+                          C_LR: _f2i(self._host_lr()), C_MOM: _f2i(getattr(opt, "momentum", 0.0)),
                           C_NEST: int(getattr(opt, "nesterov", False))})
 
     # --- the step ----------------------------------------------------------------------------
@@ -1209,7 +1261,8 @@ class NativeGraphEngine(Engine):
                         self.Pb.data_ptr() + 2 * lo, max(hi - lo, 0), self.ctrl.data_ptr(),
                         self.G[self.nparam:].data_ptr(), self.opt_kind, *args, H.stream_handle(), book=book,
                         reg=tab.data_ptr() if tab is not None else 0,
-                        nreg=tab.shape[0] if tab is not None else 0, lo=lo, **clip)
+                        nreg=tab.shape[0] if tab is not None else 0, lo=lo,
+                        lr=self.lr_tab.data_ptr() if self.lr_tab is not None else 0, **clip)
 
     # forward ops
     def _w(self, nd, var):

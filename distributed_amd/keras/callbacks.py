@@ -15,6 +15,7 @@ import os
 import sys
 
 from ..utils import logging as dlog
+from .schedules import LearningRateSchedule
 from .utils import Progbar
 
 
@@ -155,6 +156,9 @@ class LearningRateScheduler(Callback):
 
     def on_epoch_begin(self, epoch, logs=None):
         opt = self.model.optimizer
+        if isinstance(opt.learning_rate, LearningRateSchedule):  # tf.keras cannot set it either
+            raise TypeError(f"LearningRateScheduler: the optimizer's learning rate is the schedule "
+                            f"{opt.learning_rate!r}, which cannot be set per epoch")
         try:
             lr = self.schedule(epoch, opt.learning_rate)
         except TypeError:

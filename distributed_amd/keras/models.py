@@ -203,7 +203,9 @@ class Model(L.Layer):
     def _get_engine(self, per_replica, global_batch):
         from ..engine import select_engine
 
-        key = (per_replica, global_batch, id(self._strategy), id(self.optimizer), id(self.loss))
+        # (a learning-rate schedule coming or going changes which engines are eligible)
+        key = (per_replica, global_batch, id(self._strategy), id(self.optimizer), id(self.loss),
+               isinstance(self.optimizer.learning_rate, float))
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.finish()

@@ -11,6 +11,9 @@ import math
 
 import torch
 
+from . import schedules
+from .schedules import LearningRateSchedule
+
 
 CLIP_MODES = ("clipvalue", "clipnorm", "global_clipnorm")
 
@@ -19,7 +22,9 @@ class Optimizer:
     def __init__(self, learning_rate=0.001, name="Optimizer", **kw):
         if "lr" in kw:  # Keras alias
             learning_rate = kw.pop("lr")
-        self._lr = float(learning_rate)
+        # a number, or a schedules.LearningRateSchedule evaluated at `iterations` every step
+        self._lr = learning_rate if isinstance(learning_rate, LearningRateSchedule) else float(learning_rate)
+        self._lr_listener = None  # weak method of the engine that mirrors the rate on a device
         # gradient clipping (tf.keras >= 2.4): at most one of clipvalue / clipnorm /
         # global_clipnorm, a finite number > 0.  Applied by the engines to the gradient the
         # update rule consumes (all-reduced mean gradient + weight-regularizer gradient), once
@@ -45,14 +50,27 @@ class Optimizer:
         self.slots = {}  # name -> flat fp32 tensor
 
     @property
-    def learning_rate(self) -> float:
+    def learning_rate(self):
         return self._lr
 
     @learning_rate.setter
     def learning_rate(self, v):
-        self._lr = float(v)
+        old, self._lr = self._lr, v if isinstance(v, LearningRateSchedule) else float(v)
+        # a schedule coming or going changes what the native engine captured (a plain
+        # number is picked up from ctrl at the next epoch, as ever)
+        if isinstance(old, LearningRateSchedule) or isinstance(v, LearningRateSchedule):
+            hook = self._lr_listener() if self._lr_listener is not None else None
+            if hook is not None:
+                hook()
 
     lr = learning_rate
+
+    def current_lr(self, step=None) -> float:
+        """The rate of the update at ``step`` (default: the current ``iterations``): the
+        number given, or the schedule evaluated there."""
+        if isinstance(self._lr, LearningRateSchedule):
+            return float(self._lr(self._iterations if step is None else int(step)))
+        return self._lr
 
     @property
     def iterations(self) -> int:
@@ -85,7 +103,8 @@ class Optimizer:
         return None, None
 
     def get_config(self):
-        c = {"name": self.name, "learning_rate": self._lr}
+        lr = schedules.serialize(self._lr) if isinstance(self._lr, LearningRateSchedule) else self._lr
+        c = {"name": self.name, "learning_rate": lr}
         mode, v = self.clipping()
         if mode is not None:  # only when set: configs without clipping are what they were
             c[mode] = v
@@ -103,13 +122,14 @@ class SGD(Optimizer):
 
     @torch.no_grad()
     def apply_flat(self, p, g):
+        lr = self.current_lr()
         if self.momentum == 0.0:
-            p.add_(g, alpha=-self._lr)
+            p.add_(g, alpha=-lr)
         else:
             v = self.slots["momentum"]
-            v.mul_(self.momentum).add_(g, alpha=-self._lr)
+            v.mul_(self.momentum).add_(g, alpha=-lr)
             if self.nesterov:
-                p.add_(v, alpha=self.momentum).add_(g, alpha=-self._lr)
+                p.add_(v, alpha=self.momentum).add_(g, alpha=-lr)
             else:
                 p.add_(v)
         self._iterations += 1
@@ -135,7 +155,7 @@ class Adam(Optimizer):
         m, v = self.slots["m"], self.slots["v"]
         m.mul_(self.beta_1).add_(g, alpha=1 - self.beta_1)
         v.mul_(self.beta_2).addcmul_(g, g, value=1 - self.beta_2)
-        lr_t = self._lr * math.sqrt(1 - self.beta_2 ** t) / (1 - self.beta_1 ** t)
+        lr_t = self.current_lr() * math.sqrt(1 - self.beta_2 ** t) / (1 - self.beta_1 ** t)
         if self.amsgrad:
             vh = self.slots["vhat"]
             torch.maximum(vh, v, out=vh)
@@ -168,7 +188,7 @@ class RMSprop(Optimizer):
             mg = self.slots["mg"]
             mg.mul_(self.rho).add_(g, alpha=1 - self.rho)
             denom = ms - mg * mg
-        upd = g / (denom.sqrt() + self.epsilon) * self._lr
+        upd = g / (denom.sqrt() + self.epsilon) * self.current_lr()
         if self.momentum:
             mom = self.slots["momentum"]
             mom.mul_(self.momentum).add_(upd)
@@ -195,6 +215,9 @@ def get(identifier) -> Optimizer:
     if isinstance(identifier, dict):
         cfg = dict(identifier.get("config", {}))
         cfg.pop("decay", None)
+        for k in ("learning_rate", "lr"):
+            if isinstance(cfg.get(k), dict):
+                cfg[k] = schedules.deserialize(cfg[k])
         return _CLASSES[identifier["class_name"]](**cfg)
     raise ValueError(f"unknown optimizer {identifier!r}")
 

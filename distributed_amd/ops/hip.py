@@ -1256,6 +1256,89 @@ def grad_norm(G, plan: ClipPlan, c, P=None):
                    stream_handle())
 
 
+LR_MAX_BOUNDS = 16  # layer_ops.h LR_MAX_BOUNDS: boundaries of a PiecewiseConstantDecay in the descriptor
+LR_MAX_STEPS = 1 << 24  # layer_ops.h LR_MAX_STEPS: decay_steps / warmup_steps, exact as a float
+LR_WORDS = 44  # layer_ops.h LrSched
+LR_KINDS = {"ExponentialDecay": 1, "InverseTimeDecay": 2, "PolynomialDecay": 3, "PiecewiseConstantDecay": 4,
+            "CosineDecay": 5}  # layer_ops.h LR_*
+
+
+def lr_schedule_ok(schedule):
+    """(ok, reason): ``schedule`` fits ``opt_step``'s descriptor -- exactly one of the five
+    keras/schedules.py classes, integral ``decay_steps`` in [1, 2^24] and ``warmup_steps`` in
+    [0, 2^24], integer boundaries (at most LR_MAX_BOUNDS, within int32), finite parameters."""
+    name = type(schedule).__name__
+    from ..keras import schedules as S
+
+    if type(schedule) is not getattr(S, name, None) or name not in LR_KINDS:
+        return False, f"learning-rate schedule {name}"
+    why = f"learning-rate schedule {name}: "
+
+    def integral(v, lo, hi):
+        return isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+
+    floats = []
+    if name == "PiecewiseConstantDecay":
+        if len(schedule.boundaries) > LR_MAX_BOUNDS:
+            return False, (f"learning-rate schedule: {len(schedule.boundaries)} boundaries exceed the table cap "
+                           f"{LR_MAX_BOUNDS}")
+        if not all(integral(b, -2 ** 31, 2 ** 31 - 1) for b in schedule.boundaries):
+            return False, why + "boundaries are not 32-bit integers"
+        floats = list(schedule.values)
+    else:
+        if not integral(schedule.decay_steps, 1, LR_MAX_STEPS):
+            return False, why + f"decay_steps {schedule.decay_steps!r} is not an integer in [1, 2^24]"
+        floats = [schedule.initial_learning_rate]
+        if name in ("ExponentialDecay", "InverseTimeDecay"):
+            floats.append(schedule.decay_rate)
+        elif name == "PolynomialDecay":
+            floats += [schedule.end_learning_rate, schedule.power]
+        else:
+            floats.append(schedule.alpha)
+            if schedule.warmup_target is not None:
+                floats.append(schedule.warmup_target)
+                if not integral(schedule.warmup_steps, 0, LR_MAX_STEPS):
+                    return False, why + f"warmup_steps {schedule.warmup_steps!r} is not an integer in [0, 2^24]"
+    if not all(math.isfinite(f) and abs(f) <= 3.4028234663852886e38 for f in floats):
+        return False, why + "a parameter is not a finite float32"
+    return True, ""
+
+
+def lr_table(schedule, device=None) -> torch.Tensor:
+    """``opt_step``'s learning-rate schedule descriptor (layer_ops.h LrSched): int32
+    [LR_WORDS] -- kind, flags, decay_steps, warmup_steps, three float parameters as bits, the
+    number of boundaries, LR_MAX_BOUNDS boundaries, LR_MAX_BOUNDS + 1 values as bits.  The
+    kernel takes it by value, as a kernel argument, so it lives in HOST memory whatever
+    ``device`` the step runs on (torch allocates it 64-byte aligned); keep the tensor alive
+    for the call only -- a captured step holds its own copy."""
+    ok, why = lr_schedule_ok(schedule)
+    if not ok:
+        raise ValueError(f"lr_table: {why}")
+    if _C().LR_WORDS != LR_WORDS or _C().LR_MAX_BOUNDS != LR_MAX_BOUNDS:
+        raise RuntimeError("ops/hip.py LR_WORDS / LR_MAX_BOUNDS do not match the native build")
+    name = type(schedule).__name__
+    w = np.zeros(LR_WORDS, dtype=np.int32)
+    f = w.view(np.float32)
+    w[0] = LR_KINDS[name]
+    if name == "PiecewiseConstantDecay":
+        nb = len(schedule.boundaries)
+        w[7] = nb
+        w[8:8 + nb] = schedule.boundaries
+        f[24:24 + nb + 1] = schedule.values
+    else:
+        w[2] = schedule.decay_steps
+        f[4] = schedule.initial_learning_rate
+        if name in ("ExponentialDecay", "InverseTimeDecay"):
+            w[1], f[5] = int(schedule.staircase), schedule.decay_rate
+        elif name == "PolynomialDecay":
+            w[1], f[5], f[6] = int(schedule.cycle), schedule.end_learning_rate, schedule.power
+        else:
+            f[5] = schedule.alpha
+            if schedule.warmup_target is not None:
+                w[1], w[3], f[6] = 1, schedule.warmup_steps, schedule.warmup_target
+    return torch.from_numpy(w)
+
+
 def cast_bf16(x, y):
     _C().cast_f32_bf16(_ptr(x), _ptr(y), x.numel(), stream_handle())
 

@@ -157,6 +157,49 @@ def clip_grad(g, table, mode, c):
     return norms, scales
 
 
+def lr_schedule32(schedule, step) -> float:
+    """The fp32 host mirror of opt_step's device-side learning-rate schedule (layer_ops.hip
+    lr_eval): one of the five keras/schedules.py classes at the integer ``step``, the same
+    operations in the same order in ``numpy.float32``, all step logic in integers.  Returns
+    the float32 as a Python float."""
+    import numpy as np
+
+    f = np.float32
+    step = max(int(step), 0)
+    name = type(schedule).__name__
+    if name == "PiecewiseConstantDecay":
+        v = schedule.values[0]
+        for i, b in enumerate(schedule.boundaries):
+            if step > int(b):
+                v = schedule.values[i + 1]
+        return float(f(v))
+    ds = int(schedule.decay_steps)
+    init = f(schedule.initial_learning_rate)
+    if name in ("ExponentialDecay", "InverseTimeDecay"):
+        p = f(step // ds) if schedule.staircase else f(step) / f(ds)
+        a = f(schedule.decay_rate)
+        if name == "ExponentialDecay":
+            return float(init * np.power(a, p, dtype=f))
+        return float(init / (f(1) + a * p))
+    if name == "PolynomialDecay":
+        s, d = min(step, ds), ds
+        if schedule.cycle:
+            s, d = step, ds * max(1, (step + ds - 1) // ds)
+        end = f(schedule.end_learning_rate)
+        return float((init - end) * np.power(f(1) - f(s) / f(d), f(schedule.power), dtype=f) + end)
+    if name != "CosineDecay":
+        raise ValueError(f"lr_schedule32: no device form of {name}")
+    if schedule.warmup_target is not None:
+        ws, target = int(schedule.warmup_steps), f(schedule.warmup_target)
+        if step < ws:
+            return float(init + (target - init) * f(step) / f(ws))
+        init, step = target, step - ws
+    s = min(step, ds)
+    c = np.cos(f(np.pi) * f(s) / f(ds), dtype=f)
+    a = f(schedule.alpha)
+    return float(init * ((f(1) - a) * f(0.5) * (f(1) + c) + a))
+
+
 def sparse_softmax_xent(logits, labels):
     """Per-sample loss of SparseCategoricalCrossentropy(from_logits=True)."""
     return F.cross_entropy(logits.float(), labels.long(), reduction="none")

@@ -157,6 +157,42 @@ def regularizer_l1_l2(l1=0.01, l2=0.01):
     return _keras.regularizers.l1_l2(l1=float(l1), l2=float(l2))
 
 
+# ---- learning-rate schedules (R keras: learning_rate_schedule_*) ---------------------------------
+def _r_int(v):
+    """R passes doubles: an integral one becomes an int, anything else stays as it is."""
+    return int(v) if isinstance(v, float) and v == int(v) else v
+
+
+def learning_rate_schedule_exponential_decay(initial_learning_rate, decay_steps, decay_rate, staircase=False, **kw):
+    return _keras.optimizers.schedules.ExponentialDecay(float(initial_learning_rate), _r_int(decay_steps),
+                                                        float(decay_rate), staircase=bool(staircase), **kw)
+
+
+def learning_rate_schedule_inverse_time_decay(initial_learning_rate, decay_steps, decay_rate, staircase=False, **kw):
+    return _keras.optimizers.schedules.InverseTimeDecay(float(initial_learning_rate), _r_int(decay_steps),
+                                                        float(decay_rate), staircase=bool(staircase), **kw)
+
+
+def learning_rate_schedule_polynomial_decay(initial_learning_rate, decay_steps, end_learning_rate=0.0001, power=1.0,
+                                            cycle=False, **kw):
+    return _keras.optimizers.schedules.PolynomialDecay(float(initial_learning_rate), _r_int(decay_steps),
+                                                       end_learning_rate=float(end_learning_rate), power=float(power),
+                                                       cycle=bool(cycle), **kw)
+
+
+def learning_rate_schedule_piecewise_constant_decay(boundaries, values, **kw):
+    bs = [boundaries] if isinstance(boundaries, (int, float)) else list(boundaries)
+    return _keras.optimizers.schedules.PiecewiseConstantDecay([_r_int(b) for b in bs], [float(v) for v in values],
+                                                              **kw)
+
+
+def learning_rate_schedule_cosine_decay(initial_learning_rate, decay_steps, alpha=0.0, warmup_target=None,
+                                        warmup_steps=0, **kw):
+    return _keras.optimizers.schedules.CosineDecay(
+        float(initial_learning_rate), _r_int(decay_steps), alpha=float(alpha),
+        warmup_target=None if warmup_target is None else float(warmup_target), warmup_steps=_r_int(warmup_steps), **kw)
+
+
 # ---- compile / fit / evaluate ---------------------------------------------------------------
 def compile(object, optimizer=None, loss=None, metrics=None, **kw):  # noqa: A001  (R verb name)
     object.compile(optimizer=optimizer if optimizer is not None else "rmsprop", loss=loss, metrics=metrics, **kw)
