@@ -84,6 +84,16 @@ layer_dense <- function(object = NULL, units, activation = NULL, use_bias = TRUE
 layer_dropout <- function(object = NULL, rate, name = NULL) .r()$layer_dropout(object, rate = rate, name = name)
 
 #' @export
+layer_random_flip <- function(object = NULL, mode = "horizontal_and_vertical", seed = NULL, name = NULL) {
+  .r()$layer_random_flip(object, mode = mode, seed = seed, name = name)
+}
+
+#' @export
+layer_random_crop <- function(object = NULL, height, width, seed = NULL, name = NULL) {
+  .r()$layer_random_crop(object, height = height, width = width, seed = seed, name = name)
+}
+
+#' @export
 layer_batch_normalization <- function(object = NULL, name = NULL, ...) {
   .r()$layer_batch_normalization(object, name = name, ...)
 }

@@ -118,6 +118,17 @@ __device__ __forceinline__ bf16x8 ld_frag(const uint16_t* p) {
   return *reinterpret_cast<const bf16x8*>(p);
 }
 
+// The 32-bit finalizer the counter-based draws are built from (Dropout masks, input
+// augmentation): ops/hip.py _mix32 is the host twin.
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
 // Control block shared by the fused trainer kernels and the host.  32 x 4 B.
 // Written by the host only between graph replays (stream-ordered memcpy).
 struct Ctrl {

@@ -271,6 +271,45 @@ hipError_t gather_batch(const void* x, int x_u8, float scale, const int32_t* lab
                         int HW, int Cin, int Cp, uint16_t* xb, int32_t* yb, hipStream_t s, void* zero = nullptr,
                         long zero_bytes = 0, void* zero2 = nullptr, long zero2_bytes = 0,
                         PadCastJob pc = PadCastJob{nullptr, nullptr, 0, 0, 0, 0, 0});
+// Input augmentation (csrc/kernels/augment.hip): the model's input prefix -- a chain of
+// ZeroPadding2D / RandomCrop / RandomFlip layers -- as ONE launch behind gather_batch.
+// x [B][H][W][Cp] bf16 -> y [B][Ho][Wo][Cp]: every output pixel is a whole input pixel or
+// zero (no arithmetic on values).  The stages are listed in layer order; a thread maps its
+// output pixel back through them from the last to the first:
+//   AUG_FLIP  p = {mode bits (1 left-right, 2 up-down)}: mirrors the drawn axes
+//   AUG_CROP  p = {out_h, out_w}: adds the drawn offset in [0, in - out]
+//   AUG_PAD   p = {top, bottom, left, right}: subtracts (top, left); a coordinate outside
+//             the stage's input is a pad band and the pixel is zero (whatever the earlier
+//             stages are)
+// (a stage's input size follows from H x W and the stages ahead of it.)
+// The draws of sample b are a pure function of (stage seed, t = ctrl->cur3, g = ctrl->row0 + b)
+// -- neither rank nor world size enter -- computed once per block (blockIdx.y = b) from
+// scalars: h = mix32(mix32(g ^ key) + key), key = mix32(seed + t * 0x9e3779b9); flips are
+// bits 31 (left-right) and 30 (up-down) of h, crop offsets h % (in_h - out_h + 1) and
+// mix32(h + key) % (in_w - out_w + 1).  training == 0: no flip, centred crops.
+// labels[b] < 0 (a row past the end of the data, as gather_batch marks it): zeros.
+// ops/hip.py augment_reference is the host oracle.  The table is AUG_WORDS 32-bit words in
+// HOST memory (ops/hip.py aug_table); augment checks it against the shapes (the chain leads
+// from H x W to Ho x Wo, no crop larger than its input) and hands
+// it to the kernel by value, like opt_step's LrSched: a constant of a captured step.
+constexpr int AUG_MAX_STAGES = 8;
+enum : int { AUG_FLIP = 1, AUG_CROP = 2, AUG_PAD = 3 };
+struct AugStage {
+  int32_t kind;
+  int32_t p[4];
+  uint32_t seed;
+  int32_t pad[2];
+};
+struct alignas(16) AugTable {
+  int32_t n;  // stages in use, 1 .. AUG_MAX_STAGES
+  int32_t pad[3];
+  AugStage st[AUG_MAX_STAGES];
+};
+constexpr int AUG_WORDS = sizeof(AugTable) / 4;
+static_assert(sizeof(AugTable) == 68 * 4, "ops/hip.py aug_table lays these words out");
+hipError_t augment(const uint16_t* x, uint16_t* y, const int32_t* labels, const Ctrl* ctrl, const AugTable* tab, int B,
+                   int H, int W, int Ho, int Wo, int Cp, int training, hipStream_t s);
+
 // fp32 [R][C1][C2] -> bf16 [R][C1p][C2p] (zero padding)
 hipError_t pad_cast(const float* src, int R, int C1, int C2, int C1p, int C2p, uint16_t* dst, hipStream_t s);
 // dst fp32 [R][C1][C2] += src fp32 [R][C1p][C2p] (the un-padded part)

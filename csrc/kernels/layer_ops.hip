@@ -1361,15 +1361,7 @@ __global__ __launch_bounds__(NT) void act_bwd_k(const uint16_t* dy, const uint16
 // regenerates the same mask from (seed, t, j), and a graph replay draws a fresh mask
 // because t advances on the device.  Kept elements are scaled by 1 / (1 - rate).
 // distributed_amd/engine/native_graph.py:dropout_mask_reference is the host oracle.
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-
+// (mix32: damd_common.h, shared with augment.hip)
 __global__ __launch_bounds__(NT) void dropout_k(const uint16_t* x, uint16_t* y, long n, const Ctrl* ctrl,
                                                 uint32_t seed, uint32_t thr, float scale) {
   const uint32_t key = mix32(seed + (uint32_t)ctrl->cur3 * 0x9e3779b9u);

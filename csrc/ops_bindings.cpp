@@ -407,6 +407,15 @@ void register_kernel_ops(py::module_& m) {
      py::arg("HW"), py::arg("Cin"), py::arg("Cp"), py::arg("xb"), py::arg("yb"), py::arg("s"), py::arg("zero") = 0,
      py::arg("zero_bytes") = 0, py::arg("zero2") = 0, py::arg("zero2_bytes") = 0, py::arg("pc_src") = 0,
      py::arg("pc_dst") = 0, py::arg("pc_dims") = std::vector<int>{});
+  // tab: a HOST pointer to AUG_WORDS words (ops/hip.py aug_table), read before returning
+  m.def("augment", [](U x, U y, U labels, U ctrl, U tab, int B, int H, int W, int Ho, int Wo, int Cp, int training,
+                      U s) {
+    check(damd::augment(P_<const u16>(x), P_<u16>(y), P_<const int32_t>(labels), P_<const damd::Ctrl>(ctrl),
+                        P_<const damd::AugTable>(tab), B, H, W, Ho, Wo, Cp, training, P_<ihipStream_t>(s)),
+          "augment");
+  });
+  m.attr("AUG_MAX_STAGES") = damd::AUG_MAX_STAGES;
+  m.attr("AUG_WORDS") = damd::AUG_WORDS;
   m.def("pad_cast", [](U src, int R, int C1, int C2, int C1p, int C2p, U dst, U s) {
     check(damd::pad_cast(P_<const float>(src), R, C1, C2, C1p, C2p, P_<u16>(dst), P_<ihipStream_t>(s)), "pad_cast");
   });

@@ -12,6 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ..keras import backend as K
+from ..keras.layers import augment_seeds
 from .base import Engine
 from .data import DataFeed
 
@@ -62,6 +64,7 @@ class GenericEngine(Engine):
         self._plan_regularizers()
         # gradient clipping (keras/optimizers.py): read once, when the engine is built
         self.clip_mode, self.clip_c = model.optimizer.clipping()
+        self.aug_seeds = augment_seeds(model)  # RandomFlip / RandomCrop: effective seeds, fixed per model
 
     def _plan_regularizers(self):
         """Weight penalties (keras/regularizers.py).  L1L2 on a trainable variable: a row
@@ -196,7 +199,12 @@ class GenericEngine(Engine):
         works = None
         if idx.numel() > 0 and gcount > 0:
             xb, yb = feed.x[idx], feed.y[idx]
-            out = model(xb, training=True)
+            # input augmentation draws from (seed, t, global batch slot): what the native
+            # engines read from Ctrl::cur3 and Ctrl::row0 + r (keras/backend.py AugmentContext)
+            row0 = self.rank * self.per_replica
+            with K.AugmentContext(int(model.optimizer.iterations) + 1, np.arange(row0, row0 + idx.numel()),
+                                  self.aug_seeds):
+                out = model(xb, training=True)
             ls = self.loss.per_sample(yb, out)
             loss = ls.sum() * (1.0 / gcount)
             self._tick("forward")

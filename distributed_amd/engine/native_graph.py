@@ -6,6 +6,8 @@ used for ResNet-style networks (BASELINE.json config 4) 
 other model built from the supported layers.  What happens per step (one rank):
 
     gather_batch (device cursor, uint8/fp32 -> bf16 NHWC, channel padding)
+    augment:  a ZeroPadding2D / RandomCrop / RandomFlip chain at the model input, one launch
+              (csrc/kernels/augment.hip; only for models that begin with such a chain)
     forward:  implicit-GEMM MFMA convs / dense (csrc/kernels/gemm.hip) with bias / ReLU /
               BatchNorm-statistics epilogues, fused BN(+residual)(+ReLU) apply, pooling
     loss:     softmax cross-entropy + accuracy -> dlogits and the metric tail of G
@@ -103,6 +105,19 @@ def _layer_graph(model):
         keys[id(t)] = len(keys)
         seq.append((t.layer, [keys[id(i)] for i in t.inputs], keys[id(t)]))
     return seq, 0, keys[id(model._outputs[0])], tuple(model._inputs[0].shape[1:])
+
+
+def input_prefix(seq, in_key):
+    """The model's input prefix: the maximal chain of ZeroPadding2D / RandomCrop / RandomFlip
+    entries of ``seq`` that starts at the model input, each reading a tensor nobody else
+    reads -- what the ``augment`` kernel runs as one launch behind ``gather_batch``."""
+    chain, key = [], in_key
+    while True:
+        users = [e for e in seq if key in e[1]]
+        if len(users) != 1 or type(users[0][0]).__name__ not in H.AUG_LAYERS or len(users[0][1]) != 1:
+            return chain
+        chain.append(users[0])
+        key = users[0][2]
 
 
 def _act_name(layer) -> str:
@@ -316,16 +331,25 @@ class NativeGraphEngine(Engine):
         softmax Dense, or a linear Dense under a terminal softmax layer).  A softmax
         anywhere else has no kernel."""
         try:
-            seq, _, out_key, in_shape = _layer_graph(model)
+            seq, in_key, out_key, in_shape = _layer_graph(model)
         except Exception as e:  # pragma: no cover
             return False, f"graph: {e}"
         if len(in_shape) != 3:
             return False, "input must be an image (H, W, C)"
         head_kind, head_dense, head_softmax, head_why = output_head(seq)
+        prefix = input_prefix(seq, in_key)
+        if len(prefix) > H.AUG_MAX_STAGES:
+            return False, (f"input prefix: {len(prefix)} augmentation stages exceed the cap AUG_MAX_STAGES = "
+                           f"{H.AUG_MAX_STAGES}")
+        in_prefix = {id(e[0]) for e in prefix}
         for l, ins, _ in seq:
             k = type(l).__name__
             if l is head_softmax:
                 continue  # planned away: the loss / predict tail applies it
+            if id(l) in in_prefix:
+                continue  # one augment launch behind gather_batch
+            if k in H.AUG_LAYERS:
+                return False, f"layer {k} is native only ahead of the first weight layer"
             if k not in NativeGraphEngine.SUPPORTED:
                 return False, f"layer {k}"
             act = getattr(l, "activation", None)
@@ -579,7 +603,22 @@ class NativeGraphEngine(Engine):
         tensors[in_key] = x0
         self.x0 = x0
         nodes = []
+        # the input prefix (ZeroPadding2D / RandomCrop / RandomFlip chain at the input): ONE
+        # node whatever its length, x0 -> the augmented batch, no gradient, no backward work
+        prefix = input_prefix(seq, in_key)
+        aug = None
+        if prefix:
+            from ..keras.layers import augment_seeds
+
+            stages, ho, wo = H.aug_stages([e[0] for e in prefix], augment_seeds(model), h, w)
+            aug = Node("Augment", prefix[0][0], [x0], T((B, ho, wo, self.cin_pad), needs_grad=False),
+                       {"layers": [e[0] for e in prefix], "stages": stages, "table": H.aug_table(stages)})
+            x0.consumers.append(aug)
+            tensors[prefix[-1][2]] = aug.out
+            nodes.append(aug)
         for layer, ins, ok in seq:
+            if any(layer is e[0] for e in prefix):
+                continue
             kind = type(layer).__name__
             xs = [tensors[i] for i in ins]
             shp = self._out_shape(kind, layer, xs)
@@ -603,13 +642,18 @@ class NativeGraphEngine(Engine):
             self._alias(sm.out, sm.inputs[0])
         # packed-tap stem: a <= 4-channel input read only by stride-2 convs of <= 8 columns
         # is stored with 4 channels and those convs run K = KH x 32 (ops/hip.py stem4_ok)
-        if c <= 4 and x0.consumers and env.get_bool("DAMD_STEM4", True) and all(
-                nd.kind == "Conv2D" and H.stem4_ok((B, h, w, 4), (nd.layer.kernel.shape[0], nd.layer.kernel.shape[1],
-                                                                  4, nd.layer.kernel.shape[3]),
+        # (behind an input prefix the decision is the augmented tensor's consumers' and is
+        # carried back to x0: the augment kernel moves whole pixels of either pitch)
+        xin = aug.out if aug is not None else x0
+        if c <= 4 and xin.consumers and env.get_bool("DAMD_STEM4", True) and all(
+                nd.kind == "Conv2D" and H.stem4_ok(xin.shape[:3] + (4,),
+                                                    (nd.layer.kernel.shape[0], nd.layer.kernel.shape[1],
+                                                     4, nd.layer.kernel.shape[3]),
                                                     nd.layer.strides, nd.layer.padding)
-                for nd in x0.consumers):
+                for nd in xin.consumers):
             self.cin_pad = 4
             x0.shape = (B, h, w, 4)
+            xin.shape = xin.shape[:3] + (4,)
         self._fuse()
 
     def _out_shape(self, kind, l, xs):
@@ -1369,6 +1413,14 @@ class NativeGraphEngine(Engine):
             H.bn_apply(x.buf, self._ident(C), nd.out.root().buf, relu=True)
         else:
             H.act_fwd(x.buf, nd.out.root().buf, an)
+
+    _aug_training = True  # (NativeInference: flips off, crops centred)
+
+    def _fwd_Augment(self, nd):
+        H.augment(self.x0.buf, nd.out.buf, self.labels, self.ctrl, nd.attrs["table"], self._aug_training)
+
+    def _bwd_Augment(self, nd):
+        pass  # the input has no gradient
 
     def _fwd_Dropout(self, nd):
         H.dropout(nd.inputs[0].root().buf, nd.out.root().buf, self.ctrl, nd.attrs["seed"], nd.layer.rate)

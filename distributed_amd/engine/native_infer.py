@@ -9,7 +9,9 @@ every epoch).  Here that runs on the same lowered plan as training
   any evaluation split whole) and ``gather_batch`` cuts batch ``cursor`` on the device;
 * BatchNorm runs with the MOVING statistics: ``bn_infer_st`` turns them into the same
   (mean, invstd, scale, shift) rows the training plan derives from batch statistics, so
-  the fused BN / residual / stem-pool kernels are reused unchanged; Dropout is identity;
+  the fused BN / residual / stem-pool kernels are reused unchanged; Dropout is identity; an
+  input prefix (ZeroPadding2D / RandomCrop / RandomFlip) runs its ``augment`` launch in
+  inference mode: pads as in training, crops centred, no flips;
 * one step = gather -> forward -> (``logits_store`` or, for a softmax output,
   ``softmax_store`` | ``softmax_xent`` or, for one-hot / dense targets,
   ``softmax_xent_dense``) -> ``step_fold``
@@ -39,6 +41,7 @@ class NativeInference(NativeGraphEngine):
     name = "native_infer"
     _weights_static = True
     _bn_fin = False  # BN runs from the moving statistics (bn_infer_st)
+    _aug_training = False  # an input prefix runs with flips off and crops centred
 
     @staticmethod
     def eligible(model, device, evaluate: bool = False) -> Tuple[bool, str]:

@@ -28,6 +28,34 @@ def to_snake_case(name: str) -> str:
     return s if s[0] != "_" else "private" + s
 
 
+class AugmentContext:
+    """What the input-augmentation layers draw from during a training step: the step ``t``
+    (the optimizer's iterations + 1), the global batch slot of every row of the replica's
+    batch, and the layers' effective seeds ({id(layer): seed}, keras/layers.py
+    augment_seeds).  An engine sets it around the model's forward call."""
+
+    def __init__(self, t: int, slots, seeds=None):
+        self.t, self.slots, self.seeds = int(t), slots, dict(seeds or {})
+
+    def __enter__(self):
+        global _AUGMENT
+        self._prev, _AUGMENT = _AUGMENT, self
+        return self
+
+    def __exit__(self, *exc):
+        global _AUGMENT
+        _AUGMENT = self._prev
+        return False
+
+
+_AUGMENT = None
+
+
+def augment_context():
+    """The active :class:`AugmentContext`, or None (a bare ``layer(x, training=True)``)."""
+    return _AUGMENT
+
+
 def floatx() -> str:
     return "float32"
 

@@ -5,7 +5,8 @@ Layers used by the reference model (reference README.md:58-68, 292-298):
 initializers, NHWC layout and auto-naming (``conv2d``, ``max_pooling2d``, ``flatten``,
 ``dense``, ``dense_1``).  The extra layers (BatchNormalization, Add, pooling variants,
 ZeroPadding2D, Activation, Dropout, Reshape, Input) support the functional API and
-ResNet-18 (BASELINE.json:10).
+ResNet-18 (BASELINE.json:10); RandomFlip / RandomCrop are the input augmentation of its
+training recipe.
 """
 from __future__ import annotations
 
@@ -594,6 +595,115 @@ class ZeroPadding2D(Layer):
         return c
 
 
+class _RandomAugment(Layer):
+    """Input augmentation drawn per sample from (effective seed, step t, global batch slot g)
+    -- ops/hip.py aug_draws, the definition every engine shares: no RNG state, the same
+    sample transform at any world size, and a resumed run continues the sequence.  t, g and
+    the seed come from the engine's :class:`~backend.AugmentContext`; a bare
+    ``layer(x, training=True)`` uses t = 1, g = 0 .. batch - 1 and the layer's own seed at
+    position 0."""
+
+    def _draw_args(self, x):
+        from ..ops import hip as _hip
+
+        ctx = K.augment_context()
+        if ctx is None:
+            return _hip.aug_seed(self.seed, 0), 1, np.arange(x.shape[0])
+        seed = ctx.seeds.get(id(self), _hip.aug_seed(self.seed, 0))
+        g = ctx.slots
+        g = g.detach().cpu().numpy() if isinstance(g, torch.Tensor) else np.asarray(g)
+        if len(g) != x.shape[0]:
+            raise ValueError(f"{type(self).__name__}: {len(g)} batch slots for {x.shape[0]} rows")
+        return seed, ctx.t, g
+
+
+class RandomFlip(_RandomAugment):
+    """Keras RandomFlip.  Training: each sample is flipped left-right (``"horizontal"``)
+    and / or up-down (``"vertical"``), each with probability 1/2, the two axes drawn
+    independently.  Inference: identity."""
+
+    def __init__(self, mode="horizontal_and_vertical", seed=None, **kw):
+        super().__init__(**kw)
+        if mode not in ("horizontal", "vertical", "horizontal_and_vertical"):
+            raise ValueError(f"RandomFlip: mode must be 'horizontal', 'vertical' or 'horizontal_and_vertical', "
+                             f"got {mode!r}")
+        self.mode, self.seed = mode, seed
+
+    def call(self, x, training=False):
+        if not training:
+            return x
+        from ..ops import hip as _hip
+
+        seed, t, g = self._draw_args(x)
+        lr, ud = _hip.aug_flip_bits(seed, t, g, _hip.AUG_FLIP_MODES[self.mode])
+        for bits, axis in ((lr, 2), (ud, 1)):
+            if bits.any():
+                m = torch.from_numpy(bits).to(x.device).view(-1, 1, 1, 1)
+                x = torch.where(m, x.flip(axis), x)
+        return x
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(mode=self.mode, seed=self.seed)
+        return c
+
+
+class RandomCrop(_RandomAugment):
+    """Keras RandomCrop.  Training: each sample keeps a ``height`` x ``width`` window at an
+    integer offset drawn per axis as a 32-bit hash reduced modulo the number of offsets
+    (H - height + 1, W - width + 1) -- uniform up to the modulo's bias of at most range / 2^32.
+    Inference: the centre window, at offsets (H - height) // 2 and (W - width) // 2.  An
+    input smaller than the target raises ValueError when the layer is built (no resize)."""
+
+    def __init__(self, height, width, seed=None, **kw):
+        super().__init__(**kw)
+        self.height, self.width, self.seed = int(height), int(width), seed
+        if self.height < 1 or self.width < 1:
+            raise ValueError(f"RandomCrop: height and width must be >= 1, got {height} x {width}")
+        if self._batch_input_shape is not None:
+            self._maybe_build(self._batch_input_shape)
+
+    def build(self, input_shape):
+        h, w = input_shape[1], input_shape[2]
+        if (h is not None and h < self.height) or (w is not None and w < self.width):
+            raise ValueError(f"RandomCrop({self.height}, {self.width}): the input {h} x {w} is smaller than the "
+                             "target and there is no resize path")
+
+    def compute_output_shape(self, s):
+        return (s[0], self.height, self.width, s[3])
+
+    def call(self, x, training=False):
+        h, w = x.shape[1], x.shape[2]
+        if h < self.height or w < self.width:
+            raise ValueError(f"RandomCrop({self.height}, {self.width}): the input {h} x {w} is smaller than the target")
+        if not training:
+            oy, ox = (h - self.height) // 2, (w - self.width) // 2
+            return x[:, oy:oy + self.height, ox:ox + self.width]
+        from ..ops import hip as _hip
+
+        seed, t, g = self._draw_args(x)
+        oy, ox = _hip.aug_crop_offsets(seed, t, g, h - self.height + 1, w - self.width + 1)
+        rows = torch.from_numpy(oy[:, None] + np.arange(self.height)[None, :]).to(x.device)
+        cols = torch.from_numpy(ox[:, None] + np.arange(self.width)[None, :]).to(x.device)
+        b = torch.arange(x.shape[0], device=x.device).view(-1, 1, 1)
+        return x[b, rows[:, :, None], cols[:, None, :]]
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(height=self.height, width=self.width, seed=self.seed)
+        return c
+
+
+def augment_seeds(model) -> dict:
+    """{id(layer): effective seed} of ``model``'s RandomFlip / RandomCrop layers: the layer's
+    ``seed`` and its position among the model's layers (the input layer not counted) through
+    ops/hip.py aug_seed -- the one definition every engine uses."""
+    from ..ops import hip as _hip
+
+    ls = [l for l in model.layers if not isinstance(l, InputLayer)]
+    return {id(l): _hip.aug_seed(l.seed, i) for i, l in enumerate(ls) if isinstance(l, _RandomAugment)}
+
+
 class BatchNormalization(Layer):
     """Keras BN over channels (axis=-1).  Under MWMS the batch statistics are per
     replica, as tf.keras 2.0's (non-synced) BatchNormalization; the moving
@@ -650,4 +760,4 @@ def add(inputs):
 
 LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
-    Reshape, Dense, Activation, ReLU, Softmax, Dropout, ZeroPadding2D, BatchNormalization, Add)}
+    Reshape, Dense, Activation, ReLU, Softmax, Dropout, ZeroPadding2D, RandomFlip, RandomCrop, BatchNormalization, Add)}

@@ -590,6 +590,8 @@ def _layer_from_config(lc: dict) -> L.Layer:
     cfg = dict(lc["config"])
     cfg.pop("dtype", None)
     for k in _IGNORED_CFG:
+        if k == "seed" and issubclass(cls, L._RandomAugment):
+            continue  # part of the (seed, t, g) draw: a reloaded model continues the sequence
         cfg.pop(k, None)
     for k in L._UNSUPPORTED_KW:  # (a non-None value reaches the layer, which warns)
         if cfg.get(k) is None:

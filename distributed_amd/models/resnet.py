@@ -11,6 +11,9 @@ shortcuts) -> GlobalAveragePooling -> Dense(classes) logits.  Convs have no bias
 ``widths``/``blocks``/``input_shape`` shrink it for tests; the graph shape stays the same.
 ``weight_decay`` puts ``regularizers.l2(weight_decay)`` on every conv and dense kernel (the
 usual Keras ResNet recipe); None (default) builds the model without regularizers.
+``augmentation`` is a list of input layers (ZeroPadding2D / RandomCrop / RandomFlip) applied
+to the input ahead of the stem, e.g. pad 4 / crop / flip for CIFAR-size images; ``input_shape``
+is then the shape of the data, not of the stem's input.
 """
 from __future__ import annotations
 
@@ -33,13 +36,16 @@ def _basic_block(x, filters, stride, name, layers, reg=None):
 
 
 def resnet18(classes: int = 1000, input_shape=(224, 224, 3), widths=(64, 128, 256, 512), blocks=(2, 2, 2, 2),
-             name: str = "resnet18", weight_decay=None):
+             name: str = "resnet18", weight_decay=None, augmentation=None):
     from ..keras import Model, layers, regularizers
 
     reg = regularizers.l2(weight_decay) if weight_decay is not None else None
     inp = layers.Input(shape=input_shape, name="input_1")
+    x = inp
+    for aug in augmentation or ():
+        x = aug(x)
     x = layers.Conv2D(widths[0], 7, strides=2, padding="same", use_bias=False, kernel_regularizer=reg,
-                      name="conv1_conv")(inp)
+                      name="conv1_conv")(x)
     x = layers.BatchNormalization(epsilon=1.001e-5, name="conv1_bn")(x)
     x = layers.Activation("relu", name="conv1_relu")(x)
     x = layers.MaxPooling2D(3, strides=2, padding="same", name="pool1_pool")(x)

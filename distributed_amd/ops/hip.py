@@ -989,6 +989,138 @@ def dropout_mask_reference(n: int, seed: int, t: int, rate: float) -> np.ndarray
     return h >= np.uint32(thr)
 
 
+# --- input augmentation (csrc/kernels/augment.hip; layer_ops.h has the contract) ---------------
+AUG_MAX_STAGES = 8  # layer_ops.h AUG_MAX_STAGES
+AUG_WORDS = 68  # layer_ops.h AugTable
+AUG_FLIP, AUG_CROP, AUG_PAD = 1, 2, 3
+AUG_DEFAULT_SEED = 0xA06D  # a layer with seed=None
+AUG_LAYERS = ("ZeroPadding2D", "RandomCrop", "RandomFlip")
+AUG_FLIP_MODES = {"horizontal": 1, "vertical": 2, "horizontal_and_vertical": 3}
+
+
+def aug_seed(seed, position: int) -> int:
+    """The effective 32-bit seed of an augmentation layer: its ``seed`` (a fixed default for
+    None) mixed with its position among the model's layers, so two layers of one model draw
+    independently.  Neither rank nor world size enter."""
+    s0 = AUG_DEFAULT_SEED if seed is None else int(seed)
+    return (s0 * 0x9E3779B1 + (int(position) + 1) * 0x85EBCA77) & 0xFFFFFFFF
+
+
+def aug_draws(seed: int, t: int, g):
+    """(h, h2): the two 32-bit draws of global batch slots ``g`` (array) at step ``t`` under the
+    effective ``seed`` -- h = mix32(mix32(g ^ key) + key), h2 = mix32(h + key), key =
+    mix32(seed + t * 0x9E3779B9): Dropout's counter hash with the slot as the counter."""
+    g = np.asarray(g, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    with np.errstate(over="ignore"):
+        key = int(_mix32(np.array([(int(seed) + int(t) * 0x9E3779B9) & 0xFFFFFFFF], dtype=np.uint64))[0])
+        h = _mix32((_mix32(g ^ np.uint64(key)).astype(np.uint64) + np.uint64(key)) & np.uint64(0xFFFFFFFF))
+        h2 = _mix32((h.astype(np.uint64) + np.uint64(key)) & np.uint64(0xFFFFFFFF))
+    return h, h2
+
+
+def aug_flip_bits(seed: int, t: int, g, mode: int = 3):
+    """(left-right, up-down) flip decisions (bool arrays over ``g``): bits 31 and 30 of the
+    first draw, each only where ``mode`` (AUG_FLIP_MODES) has the axis."""
+    h, _ = aug_draws(seed, t, g)
+    lr = (h >> np.uint32(31)).astype(bool) & bool(mode & 1)
+    ud = ((h >> np.uint32(30)) & np.uint32(1)).astype(bool) & bool(mode & 2)
+    return lr, ud
+
+
+def aug_crop_offsets(seed: int, t: int, g, range_y: int, range_x: int):
+    """(oy, ox) crop offsets (int64 arrays over ``g``) in [0, range_y) x [0, range_x): the two
+    draws reduced modulo the ranges."""
+    h, h2 = aug_draws(seed, t, g)
+    return (h % np.uint32(range_y)).astype(np.int64), (h2 % np.uint32(range_x)).astype(np.int64)
+
+
+def aug_stages(layers, seeds, h: int, w: int):
+    """The stage list of a chain of ZeroPadding2D / RandomCrop / RandomFlip ``layers`` applied
+    to an ``h`` x ``w`` image, and the output size: ([(kind, p0, p1, p2, p3, seed)], ho, wo)
+    with the parameters of layer_ops.h.  ``seeds``: {id(layer): effective seed}
+    (keras/layers.py augment_seeds)."""
+    stages = []
+    for l in layers:
+        k = type(l).__name__
+        if k == "ZeroPadding2D":
+            (pt, pb), (pl, pr) = l.padding
+            stages.append((AUG_PAD, int(pt), int(pb), int(pl), int(pr), 0))
+            h, w = h + pt + pb, w + pl + pr
+        elif k == "RandomCrop":
+            if l.height > h or l.width > w:
+                raise ValueError(f"RandomCrop({l.height}, {l.width}) of a {h} x {w} input: there is no resize path")
+            stages.append((AUG_CROP, l.height, l.width, 0, 0, int(seeds[id(l)])))
+            h, w = l.height, l.width
+        elif k == "RandomFlip":
+            stages.append((AUG_FLIP, AUG_FLIP_MODES[l.mode], 0, 0, 0, int(seeds[id(l)])))
+        else:
+            raise ValueError(f"aug_stages: layer {k}")
+    return stages, h, w
+
+
+def aug_table(stages) -> torch.Tensor:
+    """``augment``'s stage table (layer_ops.h AugTable): int32 [AUG_WORDS] in HOST memory --
+    the stage count, then 8 words per stage (kind, four parameters, seed).  The kernel takes
+    it by value, as a kernel argument; a captured step holds its own copy."""
+    if not 1 <= len(stages) <= AUG_MAX_STAGES:
+        raise ValueError(f"aug_table: {len(stages)} stages (1 .. AUG_MAX_STAGES = {AUG_MAX_STAGES})")
+    w = np.zeros(AUG_WORDS, dtype=np.int32)
+    w[0] = len(stages)
+    for i, st in enumerate(stages):
+        w[4 + 8 * i:4 + 8 * i + 5] = st[:5]
+        w[4 + 8 * i + 5:4 + 8 * i + 6] = np.array([st[5] & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(w)
+
+
+def augment(x, y, labels, ctrl, table, training: bool):
+    """y [B, Ho, Wo, Cp] = the augmented x [B, H, W, Cp] (bf16 NHWC, Cp a multiple of 4) under
+    ``table`` (aug_table) at step ctrl.cur3 for slots ctrl.row0 + b; rows with labels[b] < 0
+    come out zero.  ``training`` False: flips off, crops centred."""
+    _chk(x, torch.bfloat16, "x")
+    _chk(y, torch.bfloat16, "y")
+    _chk(labels, torch.int32, "labels")
+    _chk(ctrl, torch.int32, "ctrl")
+    if _C().AUG_WORDS != AUG_WORDS or _C().AUG_MAX_STAGES != AUG_MAX_STAGES:
+        raise RuntimeError("ops/hip.py AUG_WORDS / AUG_MAX_STAGES do not match the native build")
+    if table.dtype != torch.int32 or table.is_cuda or table.numel() != AUG_WORDS or not table.is_contiguous():
+        raise ValueError("augment: table must be aug_table's host int32 words")
+    if x.dim() != 4 or y.dim() != 4 or x.shape[0] != y.shape[0] or x.shape[3] != y.shape[3]:
+        raise ValueError(f"augment: x {tuple(x.shape)} / y {tuple(y.shape)} must be NHWC with one batch and pitch")
+    if labels.numel() < x.shape[0] or ctrl.numel() < 32:
+        raise ValueError("augment: labels must hold one entry per row and ctrl the 32-word block")
+    B, h, w, cp = x.shape
+    _C().augment(_ptr(x), _ptr(y), _ptr(labels), _ptr(ctrl), table.data_ptr(), B, h, w, y.shape[1], y.shape[2], cp,
+                 int(bool(training)), stream_handle())
+
+
+def augment_reference(x_nhwc, stages, t: int, g0: int, training: bool) -> np.ndarray:
+    """Host oracle of ``augment``: the batch ``x_nhwc`` (array [B, H, W, C], any dtype) after
+    ``stages`` (aug_stages) at step ``t``, row b being global batch slot ``g0 + b``.  Values
+    are only moved or replaced by zero, so the result is exact in x's dtype."""
+    x = np.asarray(x_nhwc)
+    g = np.arange(x.shape[0], dtype=np.int64) + int(g0)
+    for kind, p0, p1, p2, p3, seed in stages:
+        B, h, w = x.shape[:3]
+        if kind == AUG_FLIP:
+            if training:
+                lr, ud = aug_flip_bits(seed, t, g, p0)
+                x = np.where(lr[:, None, None, None], x[:, :, ::-1], x)
+                x = np.where(ud[:, None, None, None], x[:, ::-1], x)
+        elif kind == AUG_CROP:
+            if p0 > h or p1 > w:
+                raise ValueError(f"augment_reference: crop {p0} x {p1} of a {h} x {w} input")
+            if training:
+                oy, ox = aug_crop_offsets(seed, t, g, h - p0 + 1, w - p1 + 1)
+            else:
+                oy, ox = np.full(B, (h - p0) // 2), np.full(B, (w - p1) // 2)
+            x = np.stack([x[b, oy[b]:oy[b] + p0, ox[b]:ox[b] + p1] for b in range(B)])
+        elif kind == AUG_PAD:
+            x = np.pad(x, ((0, 0), (p0, p1), (p2, p3), (0, 0)))
+        else:
+            raise ValueError(f"augment_reference: stage kind {kind}")
+    return np.ascontiguousarray(x)
+
+
 def avgpool_fwd(x, y, pool, strides, padding):
     g = pool_geo(x.shape, pool, strides, padding)
     _C().avgpool_fwd(_ptr(x), g, _ptr(y), stream_handle())

@@ -136,6 +136,15 @@ def layer_dropout(object=None, rate=0.5, name=None):
     return _add(object, _keras.layers.Dropout(rate, name=name))
 
 
+def layer_random_flip(object=None, mode="horizontal_and_vertical", seed=None, name=None):
+    return _add(object, _keras.layers.RandomFlip(mode, seed=None if seed is None else int(seed), name=name))
+
+
+def layer_random_crop(object=None, height=None, width=None, seed=None, name=None):
+    return _add(object, _keras.layers.RandomCrop(int(height), int(width), seed=None if seed is None else int(seed),
+                                                 name=name))
+
+
 def layer_batch_normalization(object=None, name=None, **kw):
     return _add(object, _keras.layers.BatchNormalization(name=name, **kw))
 
