@@ -199,6 +199,13 @@ class ConvNetTrainer : public StepExecutor {
   int batch() const { return B_; }
   // which instantiation of the step kernels a step launched now would run
   std::string step_kernels() const { return convnet2_specialised(b_, B_, PP_) ? "specialised" : "generic"; }
+  // threads per block of that step's fwd launch / launch bound of the kernel it runs
+  int fwd_threads() const { return convnet2_fwd_threads(b_, B_, PP_); }
+  int fwd_compiled_threads() const {
+    int n = 0;
+    HIP_CHECK(convnet2_fwd_compiled_threads(b_, B_, PP_, &n));
+    return n;
+  }
 
  protected:
   void enqueue_tail() override { flush(); }
@@ -389,6 +396,8 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("num_slices_bwd", &ConvNetTrainer::num_slices_bwd)
       .def_property_readonly("batch", &ConvNetTrainer::batch)
       .def_property_readonly("step_kernels", &ConvNetTrainer::step_kernels)
+      .def_property_readonly("fwd_threads", &ConvNetTrainer::fwd_threads)
+      .def_property_readonly("fwd_compiled_threads", &ConvNetTrainer::fwd_compiled_threads)
       .def_property_readonly("parity", &ConvNetTrainer::parity)
       .def_property_readonly("stream", [](ConvNetTrainer& t) { return reinterpret_cast<uintptr_t>(t.stream()); });
 

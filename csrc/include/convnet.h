@@ -100,6 +100,10 @@ hipError_t convnet2_launch_gather(const ConvNetBuffers& b, int PP, hipStream_t s
 hipError_t convnet2_set_lds_limits();
 // true: a step with these buffers / sizes runs the constant-configuration kernels
 bool convnet2_specialised(const ConvNetBuffers& b, int B, int PP);
+// threads per block the fwd launch of such a step uses, and the thread count the kernel it
+// runs was compiled for (its launch bound)
+int convnet2_fwd_threads(const ConvNetBuffers& b, int B, int PP);
+hipError_t convnet2_fwd_compiled_threads(const ConvNetBuffers& b, int B, int PP, int* out);
 // elements of the all-reduced gradient buffer
 size_t convnet_grad_count(int PP);
 }  // namespace damd

@@ -151,6 +151,15 @@ struct ConvFrag {
   int toff[8];
   uint32_t lomask[8], zmask[8];
 };
+// A conv weight as the MFMA operand takes it: bf16 hi | bf16 lo << 16 (w = hi + lo), in one
+// 32-bit LDS word.  The thread that owns the parameter's update splits it once; conv_setup
+// of every wave then only selects a half (split per wave and lane, the 16 conversions and
+// subtractions of conv_setup sat on the conv phase's VALU-issue-bound path once per wave).
+__device__ __forceinline__ float conv_w_split(float w32) {
+  const uint32_t hi = f2bf(w32), lo = bf16_lo(w32, (uint16_t)hi);
+  return __uint_as_float(hi | (lo << 16));
+}
+// cw: [288] split weights (conv_w_split), [32] fp32 biases
 __device__ __forceinline__ void conv_setup(ConvFrag& f, const float* cw, int lane) {
   const int kg = lane >> 4;
   // slot k = 8 kg + j: tap (8 kg + j) mod 9 = (j - kg) mod 9; the x-lo slots (part 1, k in
@@ -173,54 +182,72 @@ __device__ __forceinline__ void conv_setup(ConvFrag& f, const float* cw, int lan
     s16x8 t;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float w32 = cw[tapj[j] * NF + 16 * nt + (lane & 15)];
-      const uint32_t hi = f2bf(w32), lo = bf16_lo(w32, (uint16_t)hi);
-      const uint32_t wlomask = (wlo >> j) & 1u ? 0xffffu : 0u;
-      t[j] = (short)((hi ^ ((hi ^ lo) & wlomask)) & f.zmask[j]);
+      const uint32_t hl = __float_as_uint(cw[tapj[j] * NF + 16 * nt + (lane & 15)]);
+      t[j] = (short)(((wlo >> j) & 1u ? hl >> 16 : hl) & f.zmask[j]);
     }
     f.w[nt] = __builtin_bit_cast(bf16x8, t);
     f.bias[nt] = cw[OFF_BC + 16 * nt + (lane & 15)];
   }
 }
 // emit(image, pl, channel, pooled_bf16, code) for every pooled output of the slice
-template <class Emit>
+// One row tile: the A fragment (8 LDS gathers, hi/lo split), then per channel half nt one
+// MFMA and one bias / ReLU / pool / argmax epilogue.  HALF: only the channel half h (a
+// wave-uniform runtime value) -- the two halves of a tile share nothing but the A fragment,
+// so a tile split over two waves gives the same bits as one built by a single wave.
+template <bool HALF, class Emit>
+__device__ __forceinline__ void conv_tile(const ConvFrag& f, const float* xs, int p0, int r0, int lg, int rt, int h,
+                                          int lane, Emit&& emit) {
+  s16x8 at;
+  {
+    const int r = lane & 15, wi = 4 * rt + (r >> 2), sub = r & 3;
+    const int pl = wi >> lg, b = wi & ((1 << lg) - 1), pos = p0 + pl, py = pos / PO, px = pos - py * PO;
+    const float* base = xs + (b * XR + 2 * py - r0 + (sub >> 1)) * IMG + 2 * px + (sub & 1);
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = base[f.toff[j]];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t hi = f2bf(v[j]), lo = bf16_lo(v[j], (uint16_t)hi);
+      at[j] = (short)((hi ^ ((hi ^ lo) & f.lomask[j])) & f.zmask[j]);
+    }
+  }
+  const bf16x8 a = __builtin_bit_cast(bf16x8, at);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const int wo = 4 * rt + (lane >> 4), plo = wo >> lg, bo = wo & ((1 << lg) - 1);
+  auto epilogue = [&](const f32x4& cc, float bias, int ch0) __attribute__((always_inline)) {
+    float best = fmaxf(cc[0] + bias, 0.f);
+    int arg = 0;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      const float v = fmaxf(cc[j] + bias, 0.f);
+      arg = v > best ? j : arg;
+      best = fmaxf(best, v);
+    }
+    emit(bo, plo, ch0 + (lane & 15), f2bf(best), (uint8_t)(arg | (best > 0.f ? 4 : 0)));
+  };
+  if constexpr (HALF) {
+    const bf16x8 w = h ? f.w[1] : f.w[0];
+    epilogue(mfma16(a, w, zero), h ? f.bias[1] : f.bias[0], 16 * h);
+  } else {
+    const f32x4 c0 = mfma16(a, f.w[0], zero);
+    const f32x4 c1 = mfma16(a, f.w[1], zero);
+    epilogue(c0, f.bias[0], 0);
+    epilogue(c1, f.bias[1], 16);
+  }
+}
+// The slice's row tiles over the block's NW waves.  SPLIT = false: round-robin, whole tiles
+// (with 12 tiles on 8 waves four waves build two, four build one).  SPLIT = true: whole tiles
+// for the full rounds, the leftover tiles split by channel half over twice as many waves
+// (12 tiles on 8 waves: one tile plus one half tile each).
+template <int NW, bool SPLIT, class Emit>
 __device__ __forceinline__ void conv_pool(const ConvFrag& f, const float* xs, int p0, int np, int r0, int lg,
                                           int wave, int lane, Emit&& emit) {
   const int nrt = (np << lg) >> 2;  // np positions x 2^lg images / 4 windows per tile
-  for (int rt = wave; rt < nrt; rt += 8) {
-    s16x8 at;
-    {
-      const int r = lane & 15, wi = 4 * rt + (r >> 2), sub = r & 3;
-      const int pl = wi >> lg, b = wi & ((1 << lg) - 1), pos = p0 + pl, py = pos / PO, px = pos - py * PO;
-      const float* base = xs + (b * XR + 2 * py - r0 + (sub >> 1)) * IMG + 2 * px + (sub & 1);
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = base[f.toff[j]];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t hi = f2bf(v[j]), lo = bf16_lo(v[j], (uint16_t)hi);
-        at[j] = (short)((hi ^ ((hi ^ lo) & f.lomask[j])) & f.zmask[j]);
-      }
-    }
-    const bf16x8 a = __builtin_bit_cast(bf16x8, at);
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 c0 = mfma16(a, f.w[0], zero);
-    const f32x4 c1 = mfma16(a, f.w[1], zero);
-    const int wo = 4 * rt + (lane >> 4), plo = wo >> lg, bo = wo & ((1 << lg) - 1);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const f32x4 cc = nt ? c1 : c0;
-      float best = fmaxf(cc[0] + f.bias[nt], 0.f);
-      int arg = 0;
-#pragma unroll
-      for (int j = 1; j < 4; ++j) {
-        const float v = fmaxf(cc[j] + f.bias[nt], 0.f);
-        arg = v > best ? j : arg;
-        best = fmaxf(best, v);
-      }
-      emit(bo, plo, 16 * nt + (lane & 15), f2bf(best), (uint8_t)(arg | (best > 0.f ? 4 : 0)));
-    }
-  }
+  const int nfull = SPLIT ? nrt / NW * NW : nrt;
+  for (int rt = wave; rt < nfull; rt += NW) conv_tile<false>(f, xs, p0, r0, lg, rt, 0, lane, emit);
+  if constexpr (SPLIT)
+    for (int ht = wave; ht < 2 * (nrt - nfull); ht += NW)
+      conv_tile<true>(f, xs, p0, r0, lg, nfull + (ht >> 1), ht & 1, lane, emit);
 }
 
 // ---- fixed-point cross-block sums, DPP row reductions, small MFMA, SGD-or-keep ----------

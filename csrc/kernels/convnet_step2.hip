@@ -12,7 +12,8 @@
 // values, so the combine needs no extra launch and -- unlike fp32 atomics -- its result
 // does not depend on arrival order: every step is bitwise reproducible.
 //
-//   fwd (grid NS slices x IG image groups, 512 thr): the pending SGD update of the W1
+//   fwd (grid NS slices x IG image groups, 512 thr; 768 in the flagship configuration, see
+//       CfgFlagFwd): the pending SGD update of the W1
 //       slice and of the conv parameters (both double-buffered by step parity: every
 //       block updates in registers, one owner block writes the next buffer) and of
 //       b1/W2/b2 (two owner blocks); conv + bias + ReLU + 2x2 max-pool on MFMA (pooled
@@ -125,13 +126,49 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
 // (NPOS = 169 = 56 * 3 + 1 = 84 * 2 + 1): it runs the same constant-trip code with the
 // operands of positions >= NPOS staged as zeros (0 x finite leaves the fp32 MFMA / fmaf sums
 // unchanged bit for bit) and their global loads, stores and atomics predicated off.
+//
+// How the forward spreads its phases over the block's waves (fwd only; every choice moves
+// whole tiles or stores between waves, none changes a value or an order of additions):
+//   NT      threads per block (NT / 64 waves)
+//   BAL     conv + pool row tiles: 0 round-robin over the waves (the flagship's 12 tiles on 8
+//           waves: four waves build two tiles, four build one), 1 as 0 with NT = 768 (12 waves,
+//           one tile each), 2 the leftover tiles split by channel half (8 waves: one tile
+//           plus one half tile each)
+//   STORES  the pooled tile / argmax codes go to global memory 0 before dense-1 (all
+//           threads), 1 by the waves without a dense-1 tile while the others run it, 2 by all
+//           threads after the dense-1 atomics
+//   D1REG   the dense-1 waves add their accumulators to hacc straight from registers (4
+//           atomic instructions per wave, four 128-B row segments each) instead of LDS store,
+//           barrier, one 512-B row per instruction
+// The generic kernels keep 0 / 0 / 0 on 512 threads: the bitwise comparison of the two
+// instantiations (tests/test_convnet_specialised_gpu.py, test_convnet_fwd_balance_gpu.py) is
+// the check of the flagship's.  The DAMD_FWD_* macros exist for A/B builds of the variants.
+// Measured (BENCH.md, round 8): 1 / 1 / 1 is the fastest.  The conv phase itself does not gain
+// from BAL -- its 12 tiles are 3 per SIMD whatever the wave count, and the SIMD's VALU issue
+// is the limit (the waves that share a SIMD with an older one arrive last) -- but with 12
+// waves the prologue is shorter (one W1 unit per thread) and eight waves, not four, move the
+// stores while four run dense-1; BAL = 2 (a duplicated A-fragment build) loses.
+#ifndef DAMD_FWD_BAL
+#define DAMD_FWD_BAL 1
+#endif
+#ifndef DAMD_FWD_STORES
+#define DAMD_FWD_STORES 1
+#endif
+#ifndef DAMD_FWD_D1REG
+#define DAMD_FWD_D1REG 1
+#endif
 struct CfgGeneric {
   static constexpr int PP = 0, LG = 0;
   static constexpr bool B64 = false, EAGER = false, SH = true;  // SH: may be sharded (xa.world)
+  static constexpr int NT = 512, BAL = 0, STORES = 0;
+  static constexpr bool D1REG = false;
 };
 struct CfgFlagFwd {
   static constexpr int PP = 3, LG = 4;
   static constexpr bool B64 = true, EAGER = true, SH = false;
+  static constexpr int BAL = DAMD_FWD_BAL, STORES = DAMD_FWD_STORES, NT = BAL == 1 ? 768 : 512;
+  static constexpr bool D1REG = DAMD_FWD_D1REG != 0;
+  static_assert(BAL >= 0 && BAL <= 2 && STORES >= 0 && STORES <= 2, "fwd wave mapping");
 };
 struct CfgFlagBwd {
   static constexpr int PP = 2, LG = 0;
@@ -164,6 +201,10 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
                                          void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
   constexpr bool SPEC = C::PP > 0;
   static_assert(!SPEC || (C::B64 && C::EAGER && !C::SH && C::LG == 4), "the one constant configuration");
+  // threads / waves of the block, 16-byte units of the bf16 W1 slice per thread (eager)
+  constexpr int NT = C::NT, NW = NT / 64, NBQ = SPEC ? (C::PP * 32 * HID / 8 + NT - 1) / NT : 2;
+  static_assert(NT % 64 == 0 && NT >= 512 && (SPEC || NT == 512), "row staging and the deferred update map 512 threads");
+  static_assert(SPEC || (C::BAL == 0 && C::STORES == 0 && !C::D1REG), "the generic kernels keep the plain mapping");
   const int B = SPEC ? CH : bpp & 0xffff, PP = SPEC ? C::PP : bpp >> 16, lg = SPEC ? C::LG : lge & 0xff;
   const int eager = SPEC ? 1 : lge >> 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -193,24 +234,26 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   // before the ctrl block is known; kept below if their tag names this step's rows ----
   XStage<U8> xst;
   long long xt = 0;
+  // (the row-staging map covers 512 threads: the waves past them take the idle slot -1)
+  const int xslot = NT > 512 && tid >= 512 ? -1 : tid;
   if (xnext != nullptr) {
-    x_load<U8>(xst, xnext, img0, B, SPEC ? IB : B - img0, lg, r0, nrows);
+    x_load<U8>(xst, xnext, img0, B, SPEC ? IB : B - img0, lg, r0, nrows, xslot);
     xt = *xtag;
   }
   // ---- first the loads whose addresses do not depend on the ctrl block: the bf16 W1 slice
   // (eager), both parities of the conv parameters, the b1/W2/b2 triplet; the scheduling
   // barrier keeps them ahead of the ctrl load (left alone, hipcc issued the ctrl load first
   // and waited for it with the kernel arguments, then sank these below further waits) ----
-  uint4 bq[2];  // eager: the bf16 W1 slice (bwd already applied the update)
+  uint4 bq[NBQ];  // eager: the bf16 W1 slice (bwd already applied the update)
   if (eager) {
     // (lanes past the slice load nothing: at PP = 2 the second unit is all out of range, and
     // its clamped duplicate loads were 8 KB per block of wasted load bandwidth.  Written as a
     // conditional load, not a select between pointers: hipcc turns the latter into a flat
     // load from a zero vector in scratch)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NBQ; ++u) {
       bq[u] = make_uint4(0u, 0u, 0u, 0u);
-      if (tid + u * 512 < n4 / 2) bq[u] = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + u * 512];
+      if (tid + u * NT < n4 / 2) bq[u] = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + u * NT];
     }
   }
   // conv parameters: current buffer by parity; their gradient is the previous step's
@@ -220,7 +263,7 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const long long cq0 = sh ? 0 : hconv_r[NCONV + tcl], cq1 = sh ? 0 : hconv_r[tcl];
   // b1/W2/b2: the grid's last two blocks own their pending update (nobody else in this
   // launch reads them; bwd reads the updated values)
-  const int si = (lin - (nblk - 2)) * 512 + tid;
+  const int si = (lin - (nblk - 2)) * NT + tid;
   const bool small_on = lin >= nblk - 2 && si >= 0 && si < NSMALL;
   const int sic = OFF_B1 + max(0, min(si, NSMALL - 1));
   const float sp = P[sic], sg0 = sh ? 0.f : G[sic], sv = V[sic];
@@ -244,11 +287,11 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   // ---- then the ctrl-dependent loads: the batch rows unless prefetched (and, deferred
   // update, W1 by parity) ----
   const bool xhit = xnext != nullptr && xt == (((long long)c.xgen << 32) | (long long)(unsigned)(c.cursor + 1));
-  if (!xhit) x_load<U8>(xst, X, row_base, c.nsamples, SPEC ? IB : B - img0, lg, r0, nrows);
+  if (!xhit) x_load<U8>(xst, X, row_base, c.nsamples, SPEC ? IB : B - img0, lg, r0, nrows, xslot);
   // this step's rows and labels for the backward (xcur / ycur): a share per block, from the
   // prefetch when it hit (L2-hot), else from the dataset; stored at the end of the kernel
   constexpr int UPI = U8 ? NPIX / 16 : NPIX / 4;  // 16-byte units per image
-  const int xcu = lin * 512 + tid;
+  const int xcu = lin * NT + tid;
   const bool xcp = xcur != nullptr && xcu < B * UPI;
   uint4 xcv = make_uint4(0u, 0u, 0u, 0u);
   int ycv = -1;
@@ -315,8 +358,8 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   // ---- pending SGD updates ----
   if (eager) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int i = tid + u * 512;  // 8 consecutive n of row kr
+    for (int u = 0; u < NBQ; ++u) {
+      const int i = tid + u * NT;  // 8 consecutive n of row kr
       // (constant configuration: every row of the tile is written -- the short last slice's
       // rows past K with the zeros bq holds there, the dense-1 MFMAs run over all PP positions)
       if (i < (SPEC ? PP * 32 * HID / 8 : n4 / 2)) {
@@ -360,7 +403,7 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   float cwn = 0.f, cvn = 0.f;
   if (tid < NCONV) {
     sgd_or_keep(pend, cp, from_fix(cq, CINV), cv, c, cwn, cvn);
-    cw[tid] = cwn;
+    cw[tid] = tid < OFF_BC ? conv_w_split(cwn) : cwn;  // weights: split once here, not per wave and lane
     // the conv epilogue's ReLU (fmaxf) and the head's would turn a NaN parameter into 0:
     // a non-finite conv / b1 / W2 / b2 value raises ctrl.bad (loss NaN) here instead
     if (!__builtin_isfinite(cwn)) __hip_atomic_fetch_or(&ctrl->bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -387,7 +430,7 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   conv_setup(cf, cw, lane);
   stamp(sts, st, 5);
   uint8_t* csl = reinterpret_cast<uint8_t*>(cw + NCONV);  // [IB][KC] argmax codes
-  conv_pool(cf, xs, p0, npl, r0, lg, wave, lane, [&](int bo, int plo, int ch, uint16_t hb, uint8_t cd) {
+  conv_pool<NW, C::BAL == 2>(cf, xs, p0, npl, r0, lg, wave, lane, [&](int bo, int plo, int ch, uint16_t hb, uint8_t cd) {
     // (constant configuration: positions >= NPOS of the last slice were computed from rows
     // nobody staged; their pooled value is 0, their code is never stored)
     as[bo * KP + plo * 32 + ch] = SPEC && plo >= np ? (uint16_t)0 : hb;
@@ -399,29 +442,34 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   // pooled tile (feature-major [k][b]: bwd's dW1 operand) and argmax codes ([b][k]) for
   // bwd, from LDS as contiguous 8-byte / 4-byte stores instead of scattered 1-2 B stores
   // (IB / 4 = 2^(lg - 2) and K / 4 = 8 np: shifts and a multiply, not divisions)
-  for (int i = tid; i < KC * (IB / 4); i += 512) {
-    if (SPEC && i >= K * (IB / 4)) break;
-    const int kk = i >> (lg - 2), bo = 4 * (i & ((1 << (lg - 2)) - 1));
-    uint16_t v[4];
+  // t0 / nt: the calling thread's slot among the nt threads that share the stores (dense-1
+  // reads only the LDS copies, so where these stores sit is a scheduling choice: C::STORES)
+  auto store_out = [&](int t0, int nt) __attribute__((always_inline)) {
+    for (int i = t0; i < KC * (IB / 4); i += nt) {
+      if (SPEC && i >= K * (IB / 4)) break;
+      const int kk = i >> (lg - 2), bo = 4 * (i & ((1 << (lg - 2)) - 1));
+      uint16_t v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = as[(bo + e) * KP + kk];
-    uint16_t* dst = pooled + (unsigned)((p0 * NF + kk) * BP + img0 + bo);
-    if (SPEC || img0 + bo + 3 < B) {
-      *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16),
-                                                 (uint32_t)v[2] | ((uint32_t)v[3] << 16));
-    } else {
+      for (int e = 0; e < 4; ++e) v[e] = as[(bo + e) * KP + kk];
+      uint16_t* dst = pooled + (unsigned)((p0 * NF + kk) * BP + img0 + bo);
+      if (SPEC || img0 + bo + 3 < B) {
+        *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16),
+                                                   (uint32_t)v[2] | ((uint32_t)v[3] << 16));
+      } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (img0 + bo + e < B) dst[e] = v[e];
+        for (int e = 0; e < 4; ++e)
+          if (img0 + bo + e < B) dst[e] = v[e];
+      }
     }
-  }
-  for (int i = tid; i < IB * (KC / 4); i += 512) {
-    const int i8 = i >> 3, bo = npl == 3 ? (int)(((unsigned)i8 * 21846u) >> 16) : i8 >> (npl >> 1), w = i - bo * (KC / 4);
-    if ((SPEC || img0 + bo < B) && (!SPEC || 4 * w < K))
-      *reinterpret_cast<uint32_t*>(code + (unsigned)((img0 + bo) * FEAT + p0 * NF + 4 * w)) =
-          reinterpret_cast<const uint32_t*>(csl + bo * KC)[w];
-  }
-  stamp(sts, st, 7);
+    for (int i = t0; i < IB * (KC / 4); i += nt) {
+      const int i8 = i >> 3, bo = npl == 3 ? (int)(((unsigned)i8 * 21846u) >> 16) : i8 >> (npl >> 1), w = i - bo * (KC / 4);
+      if ((SPEC || img0 + bo < B) && (!SPEC || 4 * w < K))
+        *reinterpret_cast<uint32_t*>(code + (unsigned)((img0 + bo) * FEAT + p0 * NF + 4 * w)) =
+            reinterpret_cast<const uint32_t*>(csl + bo * KC)[w];
+    }
+    stamp(sts, st, 7);
+  };
+  if (C::STORES == 0) store_out(tid, NT);
   if (sh) {
     // sharded: the slice's reduced dW1 arrives as 4 units (2 halves each) from their owners,
     // pushed at the end of every owner's bwd -- waited for only now, after the conv
@@ -447,30 +495,77 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const int ko = 8 * (lane >> 4);
   const int ntiles = (IB >> 4) * 4;
   float* part = xs;  // [IB][64] (the staged rows are dead)
-  for (int t = wave; t < ntiles; t += 8) {
-    const int mt = t >> 2, nt = t & 3;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int ar = 16 * mt + (lane & 15), bn = 16 * nt + (lane & 15);
-    for (int ks = 0; ks < npl; ++ks) {
-      const bf16x8 a = ld_frag(as + ar * KP + ks * 32 + ko);
-      const bf16x8 bb = ld_frag(w1t + bn * KP + ks * 32 + ko);
-      acc = mfma16(a, bb, acc);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) part[(16 * mt + 4 * (lane >> 4) + j) * HID + bn] = acc[j];
-  }
-  stamp(sts, st, 8);
-  lds_barrier();
-  stamp(sts, st, 9);
-  // one wave instruction = one 512-B row of 64 int64 adds
   long long* hp = hacc + (long)par * B * HACC_PITCH;
-  for (int r = wave; r < (hprobe == 1 ? 0 : hprobe == 2 ? IB / 2 : IB); r += 8)
-    if (SPEC || img0 + r < B) atomic_add_i64(hp + (unsigned)((img0 + r) * HACC_PITCH + lane), to_fix(part[r * HID + lane], HSCALE, &ctrl->bad));
+  // the threads of the waves without a dense-1 tile (C::STORES == 1: they store the pooled
+  // tile and the codes meanwhile)
+  const int TD1 = ntiles * 64;
+  static_assert(!(C::D1REG || C::STORES == 1) || ((1 << C::LG) >> 4) * 4 < NW, "dense-1 tiles: one per wave, waves to spare");
+  if constexpr (C::D1REG) {
+    // one tile per wave, added to hacc from the accumulator registers: lane (q, n) holds rows
+    // 4 q .. 4 q + 3 of column n, so instruction j adds row 4 q + j of four rows' 128-B
+    // segments -- no LDS round trip, no barrier ahead of the atomics (the values are the
+    // ones the LDS path converts: part[] holds the accumulators unchanged)
+    if (wave < ntiles) {
+      const int mt = wave >> 2, nt = wave & 3;
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const int ar = 16 * mt + (lane & 15), bn = 16 * nt + (lane & 15);
+      for (int ks = 0; ks < npl; ++ks) {
+        const bf16x8 a = ld_frag(as + ar * KP + ks * 32 + ko);
+        const bf16x8 bb = ld_frag(w1t + bn * KP + ks * 32 + ko);
+        acc = mfma16(a, bb, acc);
+      }
+      stamp(sts, st, 8);
+#pragma unroll
+      for (int j = 0; j < (hprobe == 1 ? 0 : hprobe == 2 ? 2 : 4); ++j) {
+        const int r = 16 * mt + 4 * (lane >> 4) + j;
+        atomic_add_i64(hp + (unsigned)((img0 + r) * HACC_PITCH + bn), to_fix(acc[j], HSCALE, &ctrl->bad));
+      }
+    } else {
+      if (C::STORES == 1) store_out(tid - TD1, NT - TD1);
+      stamp(sts, st, 8);
+    }
+    stamp(sts, st, 9);  // (no dense-1 barrier: the slot repeats the one before)
+  } else {
+    for (int t = wave; t < ntiles; t += NW) {
+      const int mt = t >> 2, nt = t & 3;
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const int ar = 16 * mt + (lane & 15), bn = 16 * nt + (lane & 15);
+      for (int ks = 0; ks < npl; ++ks) {
+        const bf16x8 a = ld_frag(as + ar * KP + ks * 32 + ko);
+        const bf16x8 bb = ld_frag(w1t + bn * KP + ks * 32 + ko);
+        acc = mfma16(a, bb, acc);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) part[(16 * mt + 4 * (lane >> 4) + j) * HID + bn] = acc[j];
+    }
+    if (C::STORES == 1 && wave >= ntiles) store_out(tid - TD1, NT - TD1);
+    stamp(sts, st, 8);
+    lds_barrier();
+    stamp(sts, st, 9);
+    // one wave instruction = one 512-B row of 64 int64 adds
+    for (int r = wave; r < (hprobe == 1 ? 0 : hprobe == 2 ? IB / 2 : IB); r += NW)
+      if (SPEC || img0 + r < B) atomic_add_i64(hp + (unsigned)((img0 + r) * HACC_PITCH + lane), to_fix(part[r * HID + lane], HSCALE, &ctrl->bad));
+  }
+  if (C::STORES == 2) store_out(tid, NT);
   if (xcp) reinterpret_cast<uint4*>(xcur)[xcu] = xcv;
   if (xcur != nullptr && lin == 0 && tid < B) ycur[tid] = ycv;
   stamp(sts, st, 4);
-  if (st != nullptr && tid == 0 && lin < 256)
-    for (int i = 0; i < 10; ++i) st[lin * 16 + i] = sts.t[i];
+  if (st != nullptr && lin < 256) {
+    if (tid == 0)
+      for (int i = 0; i < 10; ++i) st[lin * 16 + i] = C::STORES == 1 && i == 7 ? 0ull : sts.t[i];  // (7: not wave 0's)
+    // the stamps above are wave 0's.  Slots 10-13: the view of one other wave per block
+    // (block lin: wave lin mod NW, so the grid covers every wave ~nblk / NW times) of conv
+    // setup, conv pool (its arrival at the post-conv barrier), dense-1 mfma (its arrival at
+    // the dense-1 barrier) and atomics issued; slot 14: that wave | waves per block << 8
+    const int wsel = lin % NW;
+    if (tid == 64 * wsel) {
+      st[lin * 16 + 10] = sts.t[5];
+      st[lin * 16 + 11] = sts.t[6];
+      st[lin * 16 + 12] = sts.t[8];
+      st[lin * 16 + 13] = sts.t[4];
+      st[lin * 16 + 14] = (unsigned long long)(wsel | (NW << 8));
+    }
+  }
 }
 
 template <bool U8>
@@ -497,7 +592,8 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
 // double buffer (eager: fwd reads only the bf16 copy).  The preloaded 16 dwords are the
 // pointers of the loads issued ahead of the ctrl block, the prefetch tag among them.
 template <bool U8>
-__global__ __launch_bounds__(512) void fwd_flag(const void* __restrict__ xnext, const long long* __restrict__ xtag,
+__global__ __launch_bounds__(CfgFlagFwd::NT) void fwd_flag(const void* __restrict__ xnext,
+                                                const long long* __restrict__ xtag,
                                                 uint16_t* __restrict__ w1bf, float* __restrict__ P,
                                                 float* __restrict__ V, float* __restrict__ calt,
                                                 const long long* __restrict__ hconv_r, const float* __restrict__ G,
@@ -1443,9 +1539,9 @@ static void launch2_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) 
   const int lg = convnet_f1_lg(B);
   const dim3 g1(NS, (B + (1 << lg) - 1) >> lg);
   if (convnet2_specialised(b, B, PP)) {
-    hipLaunchKernelGGL((convnet2::fwd_flag<U8>), g1, dim3(512), convnet2_fwd_lds(PP, lg), st, b.xnext, b.xtag, b.w1bf,
-                       b.P, b.V, b.calt, b.hconv, b.G, b.ctrl, b.X, b.pooled, b.code, b.hacc, b.hconv, b.stamps,
-                       b.labels, b.xcur, b.ycur, b.par_hint);
+    hipLaunchKernelGGL((convnet2::fwd_flag<U8>), g1, dim3(convnet2::CfgFlagFwd::NT), convnet2_fwd_lds(PP, lg), st,
+                       b.xnext, b.xtag, b.w1bf, b.P, b.V, b.calt, b.hconv, b.G, b.ctrl, b.X, b.pooled, b.code, b.hacc,
+                       b.hconv, b.stamps, b.labels, b.xcur, b.ycur, b.par_hint);
     return;
   }
   hipLaunchKernelGGL((convnet2::fwd<U8>), g1, dim3(512), convnet2_fwd_lds(PP, lg), st,
@@ -1479,6 +1575,20 @@ static void launch2_bwd(const ConvNetBuffers& b, int B, int PPf, hipStream_t st)
                        b.w1bf, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, b.w1bf,
                        b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.Gr ? b.Gr : b.G, xargs(b), b.xnext, b.xtag,
                        auxm);
+}
+
+int convnet2_fwd_threads(const ConvNetBuffers& b, int B, int PP) {
+  return convnet2_specialised(b, B, PP) ? convnet2::CfgFlagFwd::NT : 512;
+}
+
+hipError_t convnet2_fwd_compiled_threads(const ConvNetBuffers& b, int B, int PP, int* out) {
+  const void* f = convnet2_specialised(b, B, PP)
+                      ? (b.x_u8 ? (const void*)convnet2::fwd_flag<true> : (const void*)convnet2::fwd_flag<false>)
+                      : (b.x_u8 ? (const void*)convnet2::fwd<true> : (const void*)convnet2::fwd<false>);
+  hipFuncAttributes at;
+  const hipError_t e = hipFuncGetAttributes(&at, f);
+  if (e == hipSuccess) *out = at.maxThreadsPerBlock;
+  return e;
 }
 
 hipError_t convnet2_launch_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) {

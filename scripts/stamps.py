@@ -52,6 +52,38 @@ def main():
                 continue
             d = (col - base) / 100.0
             print(f"   {j} {nm:14s} median {statistics.median(d):7.2f}  min {d.min():7.2f}  max {d.max():7.2f} us")
+        if kn == "fwd":
+            per_wave(a)
+
+
+def per_wave(a):
+    """fwd slots 10-14: block lin records the view of wave lin mod NW (slot 14: wave | NW << 8)
+    of the phases wave 0 records in slots 5, 6, 8 and 4.  Medians over the blocks that
+    recorded the wave, in us since the block's OWN start (slot 0), so blocks that start late
+    do not blur the comparison between waves."""
+    tag = a[:, 14]
+    ok = (tag > 0) & (a[:, 0] > 0)
+    if not ok.any():
+        return
+    nw = int(tag[ok][0] >> 8)
+    names = ["conv setup", "conv pool", "dense-1 mfma", "atomics issued"]
+    print(f"fwd per wave ({nw} waves per block; median us since the block's own start; 'conv pool' = arrival at the")
+    print("   post-conv barrier, 'dense-1 mfma' = arrival at the dense-1 barrier or, without one, end of the wave's tile / stores)")
+    print("   wave  blocks  " + "  ".join(f"{nm:>14s}" for nm in names))
+
+    def line(label, rows, slots):
+        med = [statistics.median((rows[:, s] - rows[:, 0]) / 100.0) if (rows[:, s] > 0).all() else float("nan")
+               for s in slots]
+        print(f"   {label:>4s}  {len(rows):6d}  " + "  ".join(f"{m:14.2f}" for m in med))
+
+    line("0*", a[ok], (5, 6, 8, 4))  # wave 0 as every block records it
+    for w in range(nw):
+        rows = a[ok & ((tag & 0xff) == w)]
+        if len(rows):
+            line(str(w), rows, (10, 11, 12, 13))
+    late = a[ok]
+    d = (late[:, 3] - late[:, 6]) / 100.0
+    print(f"   wave 0's wait at the post-conv barrier (slot 3 - slot 6): median {statistics.median(d):.2f} us")
 
 
 if __name__ == "__main__":
