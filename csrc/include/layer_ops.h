@@ -116,7 +116,8 @@ hipError_t avgpool_bwd(const uint16_t* dy, int N, int H, int W, int C, int ph, i
 hipError_t bn_infer_st(const float* rmean, const float* rvar, const float* gamma, const float* beta, float eps, int C,
                        float* st, hipStream_t s);
 hipError_t logits_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s);
-// logits_store with a row softmax (models whose output is a probability)
+// logits_store with a row softmax (models whose output is a probability); both reject
+// K < 1, K > ld, B < 1 and a null ctrl before any launch
 hipError_t softmax_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s);
 hipError_t step_fold(Ctrl* ctrl, float* tail, hipStream_t s);
 // out = a + b (bf16)
@@ -260,6 +261,7 @@ hipError_t reg_penalty(const float* P, long n, const int32_t* reg, int nreg, flo
 // [per][HW][Cp] zero-padded channels; labels int32.  zero / zero2 (optional): byte ranges
 // (16-byte aligned, multiples of 16 bytes) cleared in the same launch -- the step's
 // gradient buffer and BatchNorm statistics accumulators, so no memset launch precedes it.
+// uint8 RGB into Cp == 4 with HW % 4 == 0 reads x as dwords: x must be 4-byte aligned.
 // A pad_cast (below) run inside gather_batch's launch: the step's first layer's padded bf16
 // weights refreshed without a launch of their own (src == nullptr: none).
 struct PadCastJob {

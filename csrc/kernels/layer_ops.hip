@@ -2527,7 +2527,7 @@ hipError_t bn_infer_st(const float* rmean, const float* rvar, const float* gamma
 }
 
 hipError_t logits_store(const float* logits, int ld, int K, int B, const Ctrl* ctrl, float* out, hipStream_t s) {
-  if (K > ld) return hipErrorInvalidValue;
+  if (K > ld || K < 1 || B < 1 || !ctrl) return hipErrorInvalidValue;
   hipLaunchKernelGGL(logits_store_k, dim3(grid_for((long)B * K)), dim3(NT), 0, s, logits, ld, K, B, ctrl, out);
   return hipGetLastError();
 }
@@ -2555,6 +2555,8 @@ hipError_t gather_batch(const void* x, int x_u8, float scale, const int32_t* lab
   if (pc.src && (!pc.dst || pc.R < 1 || pc.C1 < 1 || pc.C2 < 1 || pc.C1p < pc.C1 || pc.C2p < pc.C2))
     return hipErrorInvalidValue;
   if (Cp % 8 && !(Cp == 4 && Cin <= 4 && HW % 2 == 0)) return hipErrorInvalidValue;
+  // the RGB uint8 path (the kernel's first branch) reads x as dwords
+  if (Cp == 4 && Cin == 3 && x_u8 && HW % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 4) return hipErrorInvalidValue;
   for (int k = 0; k < 2; ++k) {
     const void* z = k ? zero2 : zero;
     const long nb = k ? zero2_bytes : zero_bytes;
