@@ -206,6 +206,12 @@ class ConvNetTrainer : public StepExecutor {
     HIP_CHECK(convnet2_fwd_compiled_threads(b_, B_, PP_, &n));
     return n;
   }
+  int bwd_threads() const { return convnet2_bwd_threads(b_, B_, PP_); }
+  int bwd_compiled_threads() const {
+    int n = 0;
+    HIP_CHECK(convnet2_bwd_compiled_threads(b_, B_, PP_, &n));
+    return n;
+  }
 
  protected:
   void enqueue_tail() override { flush(); }
@@ -285,6 +291,8 @@ PYBIND11_MODULE(_C, m) {
   m.attr("CONVNET_NGRAD") = kConvNetNGrad;
   m.attr("CONVNET_NCONV") = kConvNetNConv;
   m.def("convnet2_lds_bytes", [](int PP) { return py::make_tuple(convnet2_fwd_lds(PP, 4), convnet2_bwd_lds(PP)); });
+  // LDS bytes of the constant-configuration backward (bwd_flag) at its slice size
+  m.def("convnet2_bwd_flag_lds_bytes", [](int PP) { return convnet2_bwd_lds(PP, true); });
   m.def("convnet_num_slices", &convnet_num_slices);
   m.def("convnet_hacc_elems", &convnet_hacc_elems);
   m.def("convnet_grad_count", &convnet_grad_count);
@@ -398,6 +406,8 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("step_kernels", &ConvNetTrainer::step_kernels)
       .def_property_readonly("fwd_threads", &ConvNetTrainer::fwd_threads)
       .def_property_readonly("fwd_compiled_threads", &ConvNetTrainer::fwd_compiled_threads)
+      .def_property_readonly("bwd_threads", &ConvNetTrainer::bwd_threads)
+      .def_property_readonly("bwd_compiled_threads", &ConvNetTrainer::bwd_compiled_threads)
       .def_property_readonly("parity", &ConvNetTrainer::parity)
       .def_property_readonly("stream", [](ConvNetTrainer& t) { return reinterpret_cast<uintptr_t>(t.stream()); });
 

@@ -89,7 +89,8 @@ int convnet_num_slices(int PP);
 long convnet_hacc_elems(int B);
 int convnet_f1_lg(int B);
 size_t convnet2_fwd_lds(int PP, int lg);
-size_t convnet2_bwd_lds(int PP);
+// flagship: the LDS layout of the constant-configuration backward (bwd_flag)
+size_t convnet2_bwd_lds(int PP, bool flagship = false);
 hipError_t convnet2_launch_step(const ConvNetBuffers& b, int B, int PP, hipStream_t st);
 // the two launches separately (phase timing)
 hipError_t convnet2_launch_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st);
@@ -104,6 +105,9 @@ bool convnet2_specialised(const ConvNetBuffers& b, int B, int PP);
 // runs was compiled for (its launch bound)
 int convnet2_fwd_threads(const ConvNetBuffers& b, int B, int PP);
 hipError_t convnet2_fwd_compiled_threads(const ConvNetBuffers& b, int B, int PP, int* out);
+// the same for the bwd launch
+int convnet2_bwd_threads(const ConvNetBuffers& b, int B, int PP);
+hipError_t convnet2_bwd_compiled_threads(const ConvNetBuffers& b, int B, int PP, int* out);
 // elements of the all-reduced gradient buffer
 size_t convnet_grad_count(int PP);
 }  // namespace damd

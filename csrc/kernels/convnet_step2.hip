@@ -19,7 +19,9 @@
 //       b1/W2/b2 (two owner blocks); conv + bias + ReLU + 2x2 max-pool on MFMA (pooled
 //       tile + argmax codes stored for bwd); the dense-1 partial of the slice on MFMA,
 //       added into hacc[par][row][n] as round(v * 2^32) with 64-bit atomics.
-//   bwd (grid NS slices, 512 thr): every block converts hacc back, adds b1, and runs the
+//   bwd (grid NS slices, 512 thr; 1024 in the flagship configuration, one dh / dW1 / dP tile
+//       per wave and the conv gradient split by taps, see CfgFlagBwd): every block converts
+//       hacc back, adds b1, and runs the
 //       whole head redundantly: Dense(10) logits on f32 MFMA (16x16x4, exact fp32) with
 //       softmax-xent / accuracy / dz by 16-lane shuffles in the same waves, dh as a bf16
 //       hi+lo pair in both MFMA operand layouts in LDS (no global round trip for dh), its
@@ -157,11 +159,34 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
 #ifndef DAMD_FWD_D1REG
 #define DAMD_FWD_D1REG 1
 #endif
+//
+// How the backward spreads its phases over the block's waves (bwd only; as above, every choice
+// moves whole tiles, taps or stores between waves, none changes a value or an order of additions):
+//   NT      threads per block, 512 or 1024.  1024 (16 waves): h 4 columns per thread; logits /
+//           softmax on waves 0-3 as before; the body staged by waves 4-15 (pooled tile and input
+//           rows one slot per thread on waves 4-11, argmax codes and the W1 slice on waves
+//           12-15); dh, dW1 (+ eager update) and dP one 16x16 tile per wave; the conv gradient
+//           split by taps (threads 0-511 taps 0-4, threads 512-1023 taps 5-8 and the bias sum,
+//           each chain in its (image, position) order from zero)
+//   AUX     0 the block's aux sums and a barrier sit between dh and the dW1 MFMAs, because dps
+//           aliases the head scratch; 1 dps has its own LDS region, the barrier is gone and the
+//           aux sums run behind the dP MFMAs
+// The generic kernels keep 512 / 0.  The DAMD_BWD_* macros exist for A/B builds of the variants.
+// Measured (BENCH.md, round 9): 1024 / 1 is the fastest.  Issuing the zeroing of the dead hacc
+// parity and the next step's rows early, by the waves without a logits tile, loses at either
+// wave count; the aux sums in the tail measure the same as behind the MFMAs.
+#ifndef DAMD_BWD_NT
+#define DAMD_BWD_NT 1024
+#endif
+#ifndef DAMD_BWD_AUX
+#define DAMD_BWD_AUX 1
+#endif
 struct CfgGeneric {
   static constexpr int PP = 0, LG = 0;
   static constexpr bool B64 = false, EAGER = false, SH = true;  // SH: may be sharded (xa.world)
   static constexpr int NT = 512, BAL = 0, STORES = 0;
   static constexpr bool D1REG = false;
+  static constexpr int AUX = 0;
 };
 struct CfgFlagFwd {
   static constexpr int PP = 3, LG = 4;
@@ -173,6 +198,8 @@ struct CfgFlagFwd {
 struct CfgFlagBwd {
   static constexpr int PP = 2, LG = 0;
   static constexpr bool B64 = true, EAGER = true, SH = false;
+  static constexpr int NT = DAMD_BWD_NT, AUX = DAMD_BWD_AUX;
+  static_assert((NT == 512 || NT == 1024) && AUX >= 0 && AUX <= 1, "bwd wave mapping");
 };
 // aux elements (b1/W2/b2 gradients + metric tail) per bwd block, and a power-of-two thread
 // count per element (<= 64) that fits them in 512 threads: chunk_aux | log2(threads) << 16
@@ -735,6 +762,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   const bool sh = C::SH && xa.world > 1;  // sharded multi-rank step (see the exchange at the end)
   constexpr int cprobe = DAMD_PROBE_HCONV;  // 0 in every product build (see the top of the file)
   Stamps sts;
+  unsigned long long wst_dh = 0, wst_cg = 0;  // this wave's arrival at two barriers (slots 14 / 15)
   stamp(sts, st, 0);
   constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 1;  // (constant configuration: the grid)
   const int s = blockIdx.x, tid = threadIdx.x, NS = SPEC ? NSC : (int)gridDim.x;
@@ -745,17 +773,23 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // trip count of the slice loops: the constant PP, not np (short last slice: zero operands,
   // global loads / stores predicated off)
   const int npl = SPEC ? PP : np;
-  const int RB = max(CH * KD * 4, HEAD_BYTES);
+  // threads / waves of the block; W16: the 16-wave mapping (see CfgFlagBwd)
+  constexpr int NT = C::NT, NW = NT / 64;
+  constexpr bool W16 = NT == 1024, AUXD = C::AUX != 0;
+  static_assert(SPEC || (NT == 512 && !AUXD), "the generic kernels keep the plain mapping");
+  // (AUXD: dps behind the head scratch in a region of its own, so the head scratch stays
+  // readable to the end of the kernel; convnet2_bwd_lds sizes the flagship's LDS for it)
+  const int RB = AUXD ? HEAD_BYTES + CH * KD * 4 : max(CH * KD * 4, HEAD_BYTES);
   float* xs = reinterpret_cast<float*>(smem);                              // [CH][XR][28]
-  float* dps = reinterpret_cast<float*>(smem + XS_BYTES);                  // [CH][KD] (after the head)
+  float* dps = reinterpret_cast<float*>(smem + XS_BYTES + (AUXD ? HEAD_BYTES : 0));  // [CH][KD] (after the head)
   uint16_t* pt = reinterpret_cast<uint16_t*>(smem + XS_BYTES + RB);        // [PP*32][HP]
   uint16_t* dht = pt + PP * 32 * HP;                                       // [2][HID][HP] dh^T hi, lo
   uint16_t* dhs = dht + 2 * HID * HP;                                      // [2][CH][HP]  dh hi, lo
   uint16_t* w1s = dhs + 2 * CH * HP;                                       // [PP*32][HP]
   uint8_t* cs = reinterpret_cast<uint8_t*>(w1s + PP * 32 * HP);            // [CH][KC] argmax codes
   float* red = reinterpret_cast<float*>(pt);  // [16][320] reduction scratch, after the MFMAs
-  // head scratch (aliases dps: used before the dP MFMA of each chunk)
-  float* hs = dps;                 // [CH][HPITCH] h = relu(dense-1)
+  // head scratch (aliases dps unless AUXD: used before the dP MFMA of each chunk)
+  float* hs = reinterpret_cast<float*>(smem + XS_BYTES);  // [CH][HPITCH] h = relu(dense-1)
   float* spl = hs + CH * HPITCH;   // [716] b1[64] W2[64][10] b2[10]
   float* zs = spl + 716;           // [CH][ZP] logits, then dz
   float* rl = zs + CH * ZP;        // [CH] per-row loss
@@ -783,21 +817,29 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // previous step's reduced metric (sharded: fwd folds it from the small messages)
   const float ag_old = sh ? 0.f : Gr[OFF_LOSS + max(0, min(aec - NSMALL, 2))];
   // small parameters (b1/W2/b2, updated by fwd): 2 per thread, re-staged every chunk
-  const float spv0 = P[OFF_B1 + tid];
-  float spv1 = 0.f;
-  if (tid + 512 < NSMALL) spv1 = P[OFF_B1 + tid + 512];
-  uint4 hq0, hq1, hq2, hq3;  // hacc row (tid >> 3), columns 8 (tid & 7) .. + 8
+  // (16 waves: one per thread, threads past the 714 load nothing)
+  float spv0 = 0.f, spv1 = 0.f;
+  if (!W16 || tid < NSMALL) spv0 = P[OFF_B1 + tid];
+  if (!W16 && tid + 512 < NSMALL) spv1 = P[OFF_B1 + tid + 512];
+  // hacc row (tid >> 3), columns 8 (tid & 7) .. + 8; 16 waves: row (tid >> 4), columns
+  // 4 (tid & 15) .. + 4 in hq0 / hq1
+  constexpr int HQS = W16 ? 4 : 3, HQN = W16 ? 2 : 4;  // log2(threads per row), 16-byte units per thread
+  uint4 hq0, hq1, hq2, hq3;
   // known parity (single chunk): the head's first operand -- this step's dense-1 sums --
   // right behind b1 / W2 / b2, before the ctrl block
   const bool hq_early = ONE && phint >= 0;
   auto load_hq = [&](int chunk, int p) __attribute__((always_inline)) {
-    const int r = tid >> 3, q = tid & 7;
+    const int r = tid >> HQS, q = tid & ((1 << HQS) - 1);
     const int row = min(chunk * CH + r, B - 1);
-    const uint4* hp = reinterpret_cast<const uint4*>(hacc + (unsigned)((p * B + row) * HACC_PITCH + q * 8));
+    const uint4* hp = reinterpret_cast<const uint4*>(hacc + (unsigned)((p * B + row) * HACC_PITCH + q * 2 * HQN));
     hq0 = hp[0];
     hq1 = hp[1];
-    hq2 = hp[2];
-    hq3 = hp[3];
+    if (HQN > 2) {
+      hq2 = hp[2];
+      hq3 = hp[3];
+    } else {
+      hq2 = hq3 = make_uint4(0u, 0u, 0u, 0u);
+    }
   };
   if (hq_early) load_hq(0, phint);
   const int n8 = K * HID / 8;
@@ -805,21 +847,27 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // (only in-range units are loaded: clamped duplicates cost load bandwidth -- at PP = 2 the
   // whole second unit is out of range)
   // (conditional loads, not selects between pointers: see fwd's bq)
+  // W1 slice units wt and wt + WS: all threads, or (16 waves) waves 12-15 with two each
+  constexpr int WS = W16 ? 256 : 512;
+  const int wt = W16 ? tid - 768 : tid;  // (< 0: no W1 units)
   wv0 = wv1 = make_uint4(0u, 0u, 0u, 0u);
-  if (tid < n8) wv0 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid];
-  if ((!SPEC || 512 < PP * 32 * HID / 8) && tid + 512 < n8)
-    wv1 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + 512];
+  if (wt >= 0 && wt < n8) wv0 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[wt];
+  if ((!SPEC || WS < PP * 32 * HID / 8) && wt >= 0 && wt + WS < n8)
+    wv1 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[wt + WS];
   // the body -- pooled tile, argmax codes, input rows, read only by the MFMAs and the conv
   // gradient -- is staged by NB threads with two slots each: all 512 when chunked; in the
   // single-chunk step only waves 4-7 (slots bt and bt + 256), which have no logits to
   // compute and store it while waves 0-3 run the logits / softmax (staged by waves 0-3 too,
-  // it sat on the head's critical path)
-  constexpr int NB = ONE ? 256 : 512;
+  // it sat on the head's critical path).  16 waves: the pooled tile and the input rows on
+  // waves 4-11, one slot per thread (NB = 512); the argmax codes on waves 12-15 (slot ct)
+  constexpr int NB = W16 ? 512 : ONE ? 256 : 512;
   const int bt = ONE ? tid - 256 : tid;  // (< 0: no body slots)
-  const bool bw = !ONE || bt >= 0;
-  XStage<U8> xst, xst1;      // input rows: slot bt, and (single chunk) bt + 256
+  const bool bw = !ONE || (bt >= 0 && bt < NB);
+  const int ct = W16 ? tid - 768 : bt;   // code slot
+  const bool cw = W16 ? ct >= 0 : bw;
+  XStage<U8> xst, xst1;      // input rows: slot bt, and (single chunk, 8 waves) bt + 256
   uint4 pv0, pv1, pv2, pv3;  // pooled tile units bt + j NB (K * 8 <= 1024 units)
-  uint4 cv, cv1;             // argmax codes, units bt (+ NB), zeroed at the LDS store unless cok
+  uint4 cv, cv1;             // argmax codes, units ct (+ NB), zeroed at the LDS store unless cok
   bool cok = false, cok1 = false;
   int ylab = 0;
   bool yval = false;
@@ -856,13 +904,15 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   auto load_indep = [&](int chunk) __attribute__((always_inline)) {
     if (bw) {
       load_pv(pv0, bt, chunk);
-      load_pv(pv1, bt + NB, chunk);
+      if (NPV > 1) load_pv(pv1, bt + NB, chunk);
       if (ONE && NPV > 2) {
         load_pv(pv2, bt + 2 * NB, chunk);
         load_pv(pv3, bt + 3 * NB, chunk);
       }
-      load_cv(cv, cok, bt, chunk);
-      if (ONE && (!SPEC || NB < CH * KCM)) load_cv(cv1, cok1, bt + NB, chunk);
+    }
+    if (cw) {
+      load_cv(cv, cok, ct, chunk);
+      if (ONE && !W16 && (!SPEC || NB < CH * KCM)) load_cv(cv1, cok1, ct + NB, chunk);
     }
     if (ycur != nullptr) {  // labels and rows as this step's fwd read them: no cursor needed
       const int b = chunk * CH + min(tid, CH - 1);
@@ -870,7 +920,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       yval = tid < CH && b < B && ylab >= 0;
       if (bw) {
         x_load<U8>(xst, xcur, chunk * CH, B, B - chunk * CH, LG_CH, r0, nrows, bt);
-        if (ONE) x_load<U8>(xst1, xcur, chunk * CH, B, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
+        if (ONE && !W16) x_load<U8>(xst1, xcur, chunk * CH, B, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
       }
     }
   };
@@ -897,8 +947,9 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // 16-byte units (stored at the end; the loads travel meanwhile)
   const int ncur = next_cursor(c, cur);
   constexpr int UPI = U8 ? NPIX / 16 : NPIX / 4;  // 16-byte units per image
+  // (a block's 512 units sit on threads 0-511, as does its share of the dead hacc parity)
   const int xpu = s * 512 + tid;
-  const bool xpf = ONE && xnext != nullptr && xpu < B * UPI;
+  const bool xpf = ONE && xnext != nullptr && (!W16 || tid < 512) && xpu < B * UPI;
   uint4 xnv = make_uint4(0u, 0u, 0u, 0u);
 
   // then the ctrl-dependent ones: the dense-1 sums by parity (unless known), the labels and
@@ -914,7 +965,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       }
       if (bw) {
         x_load<U8>(xst, X, row_base + chunk * CH, c.nsamples, B - chunk * CH, LG_CH, r0, nrows, bt);
-        if (ONE) x_load<U8>(xst1, X, row_base + chunk * CH, c.nsamples, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
+        if (ONE && !W16) x_load<U8>(xst1, X, row_base + chunk * CH, c.nsamples, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
       }
     }
   };
@@ -927,8 +978,8 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // latter while waves 0-3 run the logits / softmax, so the head does not wait for the
   // input rows (the largest, last-issued loads)
   auto store_head = [&]() __attribute__((always_inline)) {
-    spl[tid] = spv0;
-    if (tid + 512 < NSMALL) spl[tid + 512] = spv1;
+    if (!W16 || tid < NSMALL) spl[tid] = spv0;
+    if (!W16 && tid + 512 < NSMALL) spl[tid + 512] = spv1;
     if (tid < CH) ylds[tid] = yval ? ylab : -1;
   };
   auto store_pv = [&](const uint4& v, int i) __attribute__((always_inline)) {
@@ -947,17 +998,19 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     }
   };
   auto store_body = [&]() __attribute__((always_inline)) {
+    if (cw) {
+      store_cv(cv, cok, ct);
+      if (ONE && !W16 && (!SPEC || NB < CH * KCM)) store_cv(cv1, cok1, ct + NB);
+    }
     if (!bw) return;
     store_pv(pv0, bt);
-    store_pv(pv1, bt + NB);
+    if (NPV > 1) store_pv(pv1, bt + NB);
     if (ONE && NPV > 2) {
       store_pv(pv2, bt + 2 * NB);
       store_pv(pv3, bt + 3 * NB);
     }
-    store_cv(cv, cok, bt);
-    if (ONE && (!SPEC || NB < CH * KCM)) store_cv(cv1, cok1, bt + NB);
     x_store<U8>(xst, xs, LG_CH, nrows);
-    if (ONE) x_store<U8>(xst1, xs, LG_CH, nrows);
+    if (ONE && !W16) x_store<U8>(xst1, xs, LG_CH, nrows);
   };
   auto store_chunk = [&](int chunk) __attribute__((always_inline)) {
     store_body();
@@ -974,9 +1027,12 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // (w1s is read only by the dP MFMAs, several barriers later)
   // (constant configuration: every row of the tile is written, rows past K as the zeros held)
   const int n8s = SPEC ? PP * 32 * HID / 8 : n8;
-  if (tid < n8s) *reinterpret_cast<uint4*>(w1s + (tid >> 3) * HP + (tid & 7) * 8) = wv0;
-  if (tid + 512 < n8s) *reinterpret_cast<uint4*>(w1s + ((tid + 512) >> 3) * HP + (tid & 7) * 8) = wv1;
+  if (wt >= 0 && wt < n8s) *reinterpret_cast<uint4*>(w1s + (wt >> 3) * HP + (wt & 7) * 8) = wv0;
+  if (wt >= 0 && wt + WS < n8s) *reinterpret_cast<uint4*>(w1s + ((wt + WS) >> 3) * HP + (wt & 7) * 8) = wv1;
 
+  // dW1 / dP tiles of the wave: 8 waves, tile rows dm0 + 2 i (one per position i); 16 waves,
+  // the one tile row dm0 = wave >> 2 (position dm0 >> 1)
+  constexpr int TPW = W16 ? 1 : MAXPP;
   const int dn = wave & 3, dm0 = wave >> 2;
   const bool mom = c.momentum != 0.f;
   float ew[ONE ? MAXPP : 1][4], ev[ONE ? MAXPP : 1][4];  // eager (single chunk only)
@@ -1003,10 +1059,34 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         if (i < np) dst[i * 64] = make_float4(accw[i][0], accw[i][1], accw[i][2], accw[i][3]);
     }
   };
-  const int ch = tid & 31, grp = tid >> 5;
+  // conv gradient: channel ch, image group grp (4 images); 16 waves: threads 0-511 accumulate
+  // taps 0-4, threads 512-1023 taps 5-8 and the bias sum (T0 .. T1 of this thread)
+  const int ch = tid & 31, grp = (tid >> 5) & 15, half = tid >> 9;
   float gw[9], gb = 0.f;
 #pragma unroll
   for (int t = 0; t < 9; ++t) gw[t] = 0.f;
+  // this block's aux elements over the chunk's rows (fixed order: deterministic); they read
+  // the head scratch only (hs, zs, rl, rc, db1p)
+  auto aux_sums = [&]() __attribute__((always_inline)) {
+    if (!aux_on) return;
+    // element order = parameter order of b1[64], W2[64][10], b2[10] (G + OFF_B1)
+    float a = 0.f;
+    if (aec < HID) {
+      if (aq == 0)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a += db1p[q * HID + aec];
+    } else if (aec < HID + HID * NCLS) {
+      const int kk = (aec - HID) / NCLS, cc = aec - HID - kk * NCLS;
+      for (int r = aq; r < CH; r += tpe) a = fmaf(hs[r * HPITCH + kk], zs[r * ZP + cc], a);
+    } else if (aec < NSMALL) {
+      const int cc = aec - HID - HID * NCLS;
+      for (int r = aq; r < CH; r += tpe) a += zs[r * ZP + cc];
+    } else if (aec < NSMALL + 2) {
+      const float* src = aec == NSMALL ? rl : rc;
+      for (int r = aq; r < CH; r += tpe) a += src[r];
+    }
+    arsum += a;
+  };
   const int nchunks = ONE ? 1 : (B + CH - 1) / CH;
 
   for (int chunk = 0; chunk < nchunks; ++chunk) {
@@ -1022,10 +1102,10 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     // MFMAs, issued once the staged operands have landed (in flight through the head)
     if (ONE && eager) {
 #pragma unroll
-      for (int i = 0; i < MAXPP; ++i) {
-        if (i >= npl) break;
-        if (SPEC && i >= np) continue;  // (short last slice: nothing to update)
-        const int mt = dm0 + 2 * i;
+      for (int i = 0; i < TPW; ++i) {
+        const int mt = W16 ? dm0 : dm0 + 2 * i, pi = W16 ? dm0 >> 1 : i;  // tile row, its position
+        if (pi >= npl) break;
+        if (SPEC && pi >= np) continue;  // (short last slice: nothing to update)
         // (one address per tile, the 4 rows at immediate offsets)
         const unsigned e0 = OFF_W1 + (unsigned)((p0 * 32 + 16 * mt + 4 * (lane >> 4)) * HID + 16 * dn + lr16);
         const float* pw = Pw + e0;
@@ -1039,21 +1119,21 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     }
     // ---- head (every block, redundantly): h = relu(hacc / 2^32 + b1) ----
     {
-      const int r = tid >> 3, q = tid & 7;
+      const int r = tid >> HQS, q = tid & ((1 << HQS) - 1);
       const bool rv = chunk * CH + r < B;
       const uint4 hq[4] = {hq0, hq1, hq2, hq3};
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < HQN; ++u) {
         const long long a = (long long)(((unsigned long long)hq[u].y << 32) | hq[u].x);
         const long long b = (long long)(((unsigned long long)hq[u].w << 32) | hq[u].z);
-        const int n = q * 8 + 2 * u;
+        const int n = q * 2 * HQN + 2 * u;
         hs[r * HPITCH + n] = rv ? fmaxf(from_fix(a, HINV) + spl[n], 0.f) : 0.f;
         hs[r * HPITCH + n + 1] = rv ? fmaxf(from_fix(b, HINV) + spl[n + 1], 0.f) : 0.f;
       }
     }
     lds_barrier();
     stamp(sts, st, 6);
-    if (ONE && wave >= 4) {  // (waves 4-7 stage the whole body: see NB above)
+    if (ONE && wave >= 4) {  // (the waves without a logits tile stage the whole body: see NB above)
       store_body();
       stamp(sts, st, 12);
     }
@@ -1121,9 +1201,10 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     // so dh^T is stored 8 bytes at a time.
     // Every LDS operand of both tiles first (dz, W2, the ReLU mask of h): one LDS wait
     // instead of three per tile -- hipcc cannot move reads above the tile's dh stores itself
-    float za[2][3], wb[2][3], hm[2][4];
+    constexpr int NDH = 16 / NW;  // (16 waves: tile = wave)
+    float za[NDH][3], wb[NDH][3], hm[NDH][4];
 #pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
+    for (int ti = 0; ti < NDH; ++ti) {
       const int t = wave + 8 * ti, mt = t >> 2, nt = t & 3, lr = lane & 15, kq = lane >> 4;
 #pragma unroll
       for (int ks = 0; ks < 3; ++ks) {
@@ -1135,7 +1216,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       for (int j = 0; j < 4; ++j) hm[ti][j] = hs[(16 * mt + 4 * kq + j) * HPITCH + 16 * nt + lr];
     }
 #pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
+    for (int ti = 0; ti < NDH; ++ti) {
       const int t = wave + 8 * ti, mt = t >> 2, nt = t & 3, lr = lane & 15, kq = lane >> 4;
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1158,35 +1239,19 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
           make_uint2((uint32_t)lo[0] | ((uint32_t)lo[1] << 16), (uint32_t)lo[2] | ((uint32_t)lo[3] << 16));
       db1p[(4 * mt + kq) * HID + n] = dsum;  // [16][64]: partial over rows rb .. rb + 3
     }
+    if (st != nullptr) wst_dh = __builtin_amdgcn_s_memrealtime();  // (this wave's arrival at the dh barrier)
     lds_barrier();
     stamp(sts, st, 8);
-    // this block's aux elements over the chunk's rows (fixed order: deterministic)
-    if (aux_on) {
-      // element order = parameter order of b1[64], W2[64][10], b2[10] (G + OFF_B1)
-      float a = 0.f;
-      if (aec < HID) {
-        if (aq == 0)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) a += db1p[q * HID + aec];
-      } else if (aec < HID + HID * NCLS) {
-        const int kk = (aec - HID) / NCLS, cc = aec - HID - kk * NCLS;
-        for (int r = aq; r < CH; r += tpe) a = fmaf(hs[r * HPITCH + kk], zs[r * ZP + cc], a);
-      } else if (aec < NSMALL) {
-        const int cc = aec - HID - HID * NCLS;
-        for (int r = aq; r < CH; r += tpe) a += zs[r * ZP + cc];
-      } else if (aec < NSMALL + 2) {
-        const float* src = aec == NSMALL ? rl : rc;
-        for (int r = aq; r < CH; r += tpe) a += src[r];
-      }
-      arsum += a;
+    if (!AUXD) {
+      aux_sums();
+      lds_barrier();  // the head scratch (dps) is overwritten by dP below
     }
-    lds_barrier();  // the head scratch (dps) is overwritten by dP below
     stamp(sts, st, 2);
     // dW1[k][n] += sum_b P[b][k] (dh_hi + dh_lo)[b][n]
 #pragma unroll
-    for (int i = 0; i < MAXPP; ++i) {
-      if (i >= npl) break;
-      const int mt = dm0 + 2 * i;
+    for (int i = 0; i < TPW; ++i) {
+      const int mt = W16 ? dm0 : dm0 + 2 * i;
+      if ((W16 ? dm0 >> 1 : i) >= npl) break;
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
         const bf16x8 a = ld_frag(pt + (16 * mt + lr16) * HP + kk * 32 + ko);
@@ -1204,10 +1269,10 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     // old bf16 slice in the prologue and nobody else touches the slice in this launch)
     if (ONE && eager) {
 #pragma unroll
-      for (int i = 0; i < MAXPP; ++i) {
-        if (i >= npl) break;
-        if (SPEC && i >= np) continue;
-        const int mt = dm0 + 2 * i;
+      for (int i = 0; i < TPW; ++i) {
+        const int mt = W16 ? dm0 : dm0 + 2 * i, pi = W16 ? dm0 >> 1 : i;
+        if (pi >= npl) break;
+        if (SPEC && pi >= np) continue;
         const unsigned e0 = OFF_W1 + (unsigned)((p0 * 32 + 16 * mt + 4 * (lane >> 4)) * HID + 16 * dn + lr16);
         float* pw = Pw + e0;
         float* vw = Vw + e0;
@@ -1226,9 +1291,9 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     {
       const int pm = wave & 3;
 #pragma unroll
-      for (int i = 0; i < MAXPP; ++i) {
-        if (i >= npl) break;
-        const int nt = (wave >> 2) + 2 * i;
+      for (int i = 0; i < TPW; ++i) {
+        if (!W16 && i >= npl) break;
+        const int nt = W16 ? wave >> 2 : (wave >> 2) + 2 * i;
         f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -1242,29 +1307,39 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         for (int j = 0; j < 4; ++j) dps[(16 * pm + 4 * (lane >> 4) + j) * KD + 16 * nt + lr16] = a4[j];
       }
     }
+    if (C::AUX == 1) aux_sums();  // (behind the MFMAs and the dP stores, nothing waits for it)
+    if (st != nullptr) wst_cg = __builtin_amdgcn_s_memrealtime();  // (arrival at the pre-conv-gradient barrier)
     lds_barrier();
     stamp(sts, st, 3);
-    // MaxPool + ReLU backward fused into the conv weight-gradient accumulation
+    // MaxPool + ReLU backward fused into the conv weight-gradient accumulation: taps T0 .. T1 - 1
+    // of this thread (all nine, or the half's), the bias sum with the last tap
+    auto conv_grad = [&](auto t0c, auto t1c) __attribute__((always_inline)) {
+      constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value;
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      const int bb = grp * 4 + ii;
-      for (int pl = 0; pl < npl; ++pl) {
-        // (short last slice: the rows of a position >= NPOS were never staged -- no 0 x garbage)
-        if (SPEC && pl >= np) continue;
-        const int cd = cs[bb * KC + pl * 32 + ch];
-        const int pos = p0 + pl, py = pos / PO, px = pos - py * PO;
-        const float dv0 = dps[bb * KD + pl * 32 + ch];
-        const float d = (cd & 4) ? dv0 : 0.f;
-        const int y0 = 2 * py + ((cd >> 1) & 1) - r0, x0 = 2 * px + (cd & 1);
-        const float* xp = xs + (bb * XR + y0) * IMG + x0;
-        float xv[9];
+      for (int ii = 0; ii < 4; ++ii) {
+        const int bb = grp * 4 + ii;
+        for (int pl = 0; pl < npl; ++pl) {
+          // (short last slice: the rows of a position >= NPOS were never staged -- no 0 x garbage)
+          if (SPEC && pl >= np) continue;
+          const int cd = cs[bb * KC + pl * 32 + ch];
+          const int pos = p0 + pl, py = pos / PO, px = pos - py * PO;
+          const float dv0 = dps[bb * KD + pl * 32 + ch];
+          const float d = (cd & 4) ? dv0 : 0.f;
+          const int y0 = 2 * py + ((cd >> 1) & 1) - r0, x0 = 2 * px + (cd & 1);
+          const float* xp = xs + (bb * XR + y0) * IMG + x0;
+          float xv[9];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) xv[t] = xp[(t / 3) * IMG + (t % 3)];
+          for (int t = T0; t < T1; ++t) xv[t] = xp[(t / 3) * IMG + (t % 3)];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) gw[t] = fmaf(d, xv[t], gw[t]);
-        gb += d;
+          for (int t = T0; t < T1; ++t) gw[t] = fmaf(d, xv[t], gw[t]);
+          if (T1 == 9) gb += d;
+        }
       }
-    }
+    };
+    using std::integral_constant;
+    if (!W16) conv_grad(integral_constant<int, 0>{}, integral_constant<int, 9>{});
+    else if (half == 0) conv_grad(integral_constant<int, 0>{}, integral_constant<int, 5>{});
+    else conv_grad(integral_constant<int, 5>{}, integral_constant<int, 9>{});
   }
   stamp(sts, st, 4);
   if (!ONE && sh) push_partials();
@@ -1281,15 +1356,17 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     }
   }
   lds_barrier();  // pt/dht region becomes `red`, dps becomes `ared`
+  // (16 waves: each half writes the taps it accumulated; red holds the same values either way)
 #pragma unroll
-  for (int t = 0; t < 9; ++t) red[grp * NCONV + t * NF + ch] = gw[t];
-  red[grp * NCONV + OFF_BC + ch] = gb;
+  for (int t = 0; t < 9; ++t)
+    if (!W16 || half == (t >= 5 ? 1 : 0)) red[grp * NCONV + t * NF + ch] = gw[t];
+  if (!W16 || half == 1) red[grp * NCONV + OFF_BC + ch] = gb;
   float* ared = dps;
-  ared[tid] = arsum;
+  if (!W16 || tid < 512) ared[tid] = arsum;  // (aux_split maps 512 threads)
   lds_barrier();
   // this slice's conv-gradient partial, fixed order over the 16 thread groups, then a
   // 64-bit fixed-point atomic add (order-independent sum over the slices)
-  for (int i = tid; i < (cprobe ? 0 : NCONV); i += 512) {
+  for (int i = tid; i < (cprobe ? 0 : NCONV); i += NT) {
     float a = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) a += red[r * NCONV + i];
@@ -1317,8 +1394,9 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // spread over the blocks
   {
     long long* hz = hacc + (long)(par ^ 1) * B * HACC_PITCH;
-    for (int i = s * 512 + tid; i < B * HID / 2; i += NS * 512)  // (32 16-B units per row)
-      *reinterpret_cast<uint4*>(hz + (i >> 5) * HACC_PITCH + (i & 31) * 2) = make_uint4(0u, 0u, 0u, 0u);
+    if (!W16 || tid < 512)
+      for (int i = s * 512 + tid; i < B * HID / 2; i += NS * 512)  // (32 16-B units per row)
+        *reinterpret_cast<uint4*>(hz + (i >> 5) * HACC_PITCH + (i & 31) * 2) = make_uint4(0u, 0u, 0u, 0u);
   }
   if (xpf) reinterpret_cast<uint4*>(xnext)[xpu] = xnv;
   if (ONE && xnext != nullptr && s == 0 && tid == 0) *xtag = ((long long)c.xgen << 32) | (long long)(unsigned)(ncur + 1);
@@ -1326,6 +1404,14 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   stamp(sts, st, 5);
   stamp_flush(sts, st, 13);
   if (st != nullptr && tid == 256) st[blockIdx.x * 16 + 13] = sts.t[12];  // wave 4's view
+  // the stamps above are wave 0's (slot 13: wave 4's).  Slots 14 / 15: the view of one wave
+  // per block (block s: wave s mod NW, so the grid covers every wave ~NS / NW times) of its
+  // arrival at the dh barrier and at the pre-conv-gradient barrier; the top byte of slot 14
+  // holds that wave, the top byte of slot 15 the waves per block
+  if (st != nullptr && tid == 64 * (s % NW)) {
+    st[blockIdx.x * 16 + 14] = (wst_dh & 0x00ffffffffffffffull) | ((unsigned long long)(s % NW) << 56);
+    st[blockIdx.x * 16 + 15] = (wst_cg & 0x00ffffffffffffffull) | ((unsigned long long)NW << 56);
+  }
 }
 
 template <bool U8, bool ONE>
@@ -1350,7 +1436,7 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
 // arguments; the aux split follows from the constant grid.  The preloaded dwords are the
 // same pointers as above and the parity hint.
 template <bool U8>
-__global__ __launch_bounds__(512) void bwd_flag(long long* __restrict__ hacc, const int* __restrict__ ycur,
+__global__ __launch_bounds__(CfgFlagBwd::NT) void bwd_flag(long long* __restrict__ hacc, const int* __restrict__ ycur,
                                                 const void* __restrict__ xcur, const float* P, const uint16_t* w1bf,
                                                 const uint16_t* __restrict__ pooled,
                                                 const uint8_t* __restrict__ code, int phint,
@@ -1499,11 +1585,15 @@ size_t convnet2_fwd_lds(int PP, int lg) {
   const size_t xsb = (size_t)IB * XR * IMG * 4, partb = (size_t)IB * HID * 4;
   return (xsb > partb ? xsb : partb) + (size_t)(IB + HID) * KP * 2 + NCONV * 4 + (size_t)IB * PP * 32 + 256 * 4;
 }
-size_t convnet2_bwd_lds(int PP) {
+// flagship: the layout of bwd_flag (CfgFlagBwd::AUX: dps in a region of its own behind the head
+// scratch instead of aliasing it)
+size_t convnet2_bwd_lds(int PP, bool flagship) {
   using namespace convnet;
   const int KD = PP * 32 + 4;
   const size_t dpsb = (size_t)CH * KD * 4;
-  const size_t rb = dpsb > (size_t)convnet2::HEAD_BYTES ? dpsb : (size_t)convnet2::HEAD_BYTES;
+  const size_t rb = flagship && convnet2::CfgFlagBwd::AUX != 0 ? (size_t)convnet2::HEAD_BYTES + dpsb
+                    : dpsb > (size_t)convnet2::HEAD_BYTES     ? dpsb
+                                                               : (size_t)convnet2::HEAD_BYTES;
   const size_t redb = (size_t)16 * NCONV * 4;  // `red` spans pt + dht after the MFMAs
   const size_t ptdht = (size_t)PP * 32 * HP * 2 + (size_t)2 * HID * HP * 2;
   return XS_BYTES + rb + (ptdht > redb ? ptdht : redb) + (size_t)2 * CH * HP * 2 + (size_t)PP * 32 * HP * 2 +
@@ -1560,7 +1650,7 @@ static void launch2_bwd(const ConvNetBuffers& b, int B, int PPf, hipStream_t st)
   // count per element (<= 64) that fits them in 512 threads
   const int auxm = convnet2::aux_split(NS);
   if (convnet2_specialised(b, B, PPf))
-    hipLaunchKernelGGL((convnet2::bwd_flag<U8>), dim3(NS), dim3(512), convnet2_bwd_lds(PP), st, b.hacc, b.ycur, b.xcur,
+    hipLaunchKernelGGL((convnet2::bwd_flag<U8>), dim3(NS), dim3(convnet2::CfgFlagBwd::NT), convnet2_bwd_lds(PP, true), st, b.hacc, b.ycur, b.xcur,
                        b.P, b.w1bf, b.pooled, b.code, b.par_hint, b.G, b.ctrl, b.X, b.labels, b.G, b.hconv, b.P, b.V,
                        b.w1bf, b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.xnext, b.xtag);
   else if (B <= CH)
@@ -1591,6 +1681,22 @@ hipError_t convnet2_fwd_compiled_threads(const ConvNetBuffers& b, int B, int PP,
   return e;
 }
 
+int convnet2_bwd_threads(const ConvNetBuffers& b, int B, int PP) {
+  return convnet2_specialised(b, B, PP) ? convnet2::CfgFlagBwd::NT : 512;
+}
+
+hipError_t convnet2_bwd_compiled_threads(const ConvNetBuffers& b, int B, int PP, int* out) {
+  const void* f = convnet2_specialised(b, B, PP)
+                      ? (b.x_u8 ? (const void*)convnet2::bwd_flag<true> : (const void*)convnet2::bwd_flag<false>)
+                  : B <= convnet::CH
+                      ? (b.x_u8 ? (const void*)convnet2::bwd<true, true> : (const void*)convnet2::bwd<false, true>)
+                      : (b.x_u8 ? (const void*)convnet2::bwd<true, false> : (const void*)convnet2::bwd<false, false>);
+  hipFuncAttributes at;
+  const hipError_t e = hipFuncGetAttributes(&at, f);
+  if (e == hipSuccess) *out = at.maxThreadsPerBlock;
+  return e;
+}
+
 hipError_t convnet2_launch_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) {
   if (!b.hacc || !b.hconv || !b.calt || B > 0xffff) return hipErrorInvalidValue;
   if (b.x_u8) launch2_fwd<true>(b, B, PP, st);
@@ -1600,7 +1706,7 @@ hipError_t convnet2_launch_fwd(const ConvNetBuffers& b, int B, int PP, hipStream
 
 hipError_t convnet2_launch_bwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) {
   if (!b.hacc || !b.hconv || !b.calt || B > 0xffff) return hipErrorInvalidValue;
-  if (convnet2_bwd_lds(ppb_of(b, PP)) > 160 * 1024) return hipErrorInvalidValue;
+  if (convnet2_bwd_lds(ppb_of(b, PP), convnet2_specialised(b, B, PP)) > 160 * 1024) return hipErrorInvalidValue;
   if (b.xa && b.xa->ppb != ppb_of(b, PP)) return hipErrorInvalidValue;
   if (b.x_u8) launch2_bwd<true>(b, B, PP, st);
   else launch2_bwd<false>(b, B, PP, st);

@@ -25,7 +25,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "scripts"))
 
 META_KEYS = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size",
-             ".kernarg_segment_size")
+             ".kernarg_segment_size", ".max_flat_workgroup_size")
 
 
 def classify(mn: str) -> str:

@@ -54,6 +54,32 @@ def main():
             print(f"   {j} {nm:14s} median {statistics.median(d):7.2f}  min {d.min():7.2f}  max {d.max():7.2f} us")
         if kn == "fwd":
             per_wave(a)
+        else:
+            per_wave_bwd(a)
+
+
+def per_wave_bwd(a):
+    """bwd slots 14 / 15: block s records the view of wave s mod NW -- its arrival at the dh
+    barrier and at the pre-conv-gradient barrier (wave 0 records the time it LEAVES them in
+    slots 8 and 3).  The top byte of slot 14 is the wave, of slot 15 the waves per block.
+    Medians over the blocks that recorded the wave, in us since the block's own start."""
+    mask = (1 << 56) - 1
+    ok = (a[:, 15] != 0) & (a[:, 0] > 0)
+    if not ok.any():
+        return
+    nw = int(a[ok][0, 15] >> 56)
+    wave = a[:, 14] >> 56
+    print(f"bwd per wave ({nw} waves per block; median us since the block's own start of the wave's ARRIVAL at the barrier;")
+    print("   '0 leaves': when wave 0 leaves it, i.e. after the last arrival)")
+    print("   wave  blocks  dh barrier  pre-conv-grad barrier")
+    rows = a[ok]
+    print(f"   0 leaves {len(rows):3d}  {statistics.median((rows[:, 8] - rows[:, 0]) / 100.0):10.2f}  "
+          f"{statistics.median((rows[:, 3] - rows[:, 0]) / 100.0):21.2f}")
+    for w in range(nw):
+        rows = a[ok & (wave == w)]
+        if len(rows):
+            d = [statistics.median(((rows[:, s] & mask) - rows[:, 0]) / 100.0) for s in (14, 15)]
+            print(f"   {w:4d}  {len(rows):6d}  {d[0]:10.2f}  {d[1]:21.2f}")
 
 
 def per_wave(a):
