@@ -1,6 +1,6 @@
-// BatchNorm statistics finalize from the fp64 accumulators (layer_ops.h BNFin), shared by
-// the consumers that finalize in their prologue: the apply kernels (layer_ops.hip) and the
-// direct conv that normalises its input on load (conv3x3.hip, GemmArgs::bnin).  One
+// BatchNorm statistics finalize from the int64 fixed-point accumulators (layer_ops.h BNFin),
+// shared by the consumers that finalize in their prologue: the apply and stem-pool kernels
+// (bn.hip, pool.hip, through layer_dev.h) and the direct conv that normalises its input on load (conv3x3.hip, GemmArgs::bnin).  One
 // definition, so every consumer derives bitwise the same coefficients.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// Non-GEMM per-layer kernels of the generic path (csrc/kernels/layer_ops.hip).
+// Non-GEMM per-layer kernels of the generic path, one kernel file per concern under
+// csrc/kernels/: bn.hip, pool.hip, loss_head.hip, optimizer.hip, glue.hip, augment.hip.
 // Activations are NHWC bf16 (uint16 storage) with the channel count C a multiple of 8,
 // parameters / statistics fp32.  All launches are stream-ordered on `s`.
 #pragma once
@@ -48,10 +49,10 @@ hipError_t bn_finalize(const float* part, int T, int C, float count, const float
 hipError_t bn_apply(const uint16_t* x, const float* st, const uint16_t* r, const float* st2, int res_mode,
                     int relu, uint16_t* y, long M, int C, hipStream_t s, const BNFin* f1 = nullptr,
                     const BNFin* f2 = nullptr);
-// inference: y = act(x*scale + shift) with scale/shift from the moving statistics
 // backward, pass 1: dz = dy * [y > 0] (relu_mask 1; relu_mask 2: y recomputed as
-// bf16(relu(x * sc + sh)) from x and st, bitwise the stored bn_apply output, y unread) ; per-block partial sums of dz and
-// dz * xhat -> part [T][2][C]; optionally writes dz (bf16).  Returns T via *T_out.
+// bf16(relu(x * sc + sh)) from x and st, bitwise the stored bn_apply output, y unread);
+// per-block partial sums of dz and dz * xhat -> part [T][2][C] (T blocks), or into acc;
+// optionally writes dz (bf16)
 hipError_t bn_bwd_reduce(const uint16_t* dy, const uint16_t* y, int relu_mask, const uint16_t* x,
                          const float* st, uint16_t* dz_out, float* part, int T, long M, int C, hipStream_t s,
                          long long* acc = nullptr, int acc_reps = 1);
@@ -60,8 +61,8 @@ int bn_bwd_blocks(long M, int C);
 void bn_reduce_reverse(bool on);
 // pass 2: dgamma/dbeta (accumulated into the gradient sinks, may be null) and the
 // coefficients co[3][C] so that dx = a*dz + b + c*xhat
-hipError_t bn_bwd_finalize(const float* part, int T, int C, float count, const float* st, const float* gamma,
-                           float* dgamma, float* dbeta, float* co, hipStream_t s);
+hipError_t bn_bwd_finalize(const float* part, int T, int C, float count, const float* st, float* dgamma,
+                           float* dbeta, float* co, hipStream_t s);
 // pass 3: dx = a*dz + b + c*xhat, dz recomputed from dy and the relu mask (bf16 out)
 hipError_t bn_bwd_apply(const uint16_t* dy, const uint16_t* y, int relu_mask, const uint16_t* x, const float* st,
                         const float* co, uint16_t* dx, long M, int C, hipStream_t s, const BNBwdFin* bf = nullptr);
@@ -77,21 +78,27 @@ hipError_t bn_bwd_apply_dual(const uint16_t* dy, const uint16_t* y, int relu_mas
                              long M, int C, hipStream_t s, const BNBwdFin& bf, const BNBwdFin& bf2);
 
 // Pooling ----------------------------------------------------------------------------------
-hipError_t maxpool_fwd(const uint16_t* x, int N, int H, int W, int C, int ph, int pw, int sh, int sw, int pad_t,
-                       int pad_l, int Ho, int Wo, uint16_t* y, uint8_t* arg, hipStream_t s);
-hipError_t maxpool_bwd(const uint16_t* dy, const uint8_t* arg, int N, int H, int W, int C, int ph, int pw, int sh,
-                       int sw, int pad_t, int pad_l, int Ho, int Wo, uint16_t* dx, hipStream_t s);
+// x [N][H][W][C], windows ph x pw, strides sh x sw, pt / pl rows / columns of padding above /
+// left of the input, y [N][Ho][Wo][C].  The field order is that of ops/hip.py pool_geo(),
+// whose 12-int list the bindings turn into this struct; the kernels take it by value.
+struct PoolGeo {
+  int N, H, W, C, ph, pw, sh, sw, pt, pl, Ho, Wo;
+};
+hipError_t maxpool_fwd(const uint16_t* x, const PoolGeo& g, uint16_t* y, uint8_t* arg, hipStream_t s);
+hipError_t maxpool_bwd(const uint16_t* dy, const uint8_t* arg, const PoolGeo& g, uint16_t* dx, hipStream_t s);
+// average pooling, divisor = in-bounds taps (TF 'same' semantics)
+hipError_t avgpool_fwd(const uint16_t* x, const PoolGeo& g, uint16_t* y, hipStream_t s);
+hipError_t avgpool_bwd(const uint16_t* dy, const PoolGeo& g, uint16_t* dx, hipStream_t s);
 // stem fusion (BatchNorm(st) -> ReLU -> MaxPool): the pool reads the conv output x
-hipError_t bn_relu_maxpool_fwd(const uint16_t* x, const float* st, int N, int H, int W, int C, int ph, int pw, int sh,
-                               int sw, int pad_t, int pad_l, int Ho, int Wo, uint16_t* y, uint8_t* arg, hipStream_t s,
-                               const BNFin* f = nullptr);
+hipError_t bn_relu_maxpool_fwd(const uint16_t* x, const float* st, const PoolGeo& g, uint16_t* y, uint8_t* arg,
+                               hipStream_t s, const BNFin* f = nullptr);
 // its backward: BN-backward partials / apply with the pool routing + ReLU mask recomputed
-hipError_t pool_bn_bwd_reduce(const uint16_t* dpool, const uint8_t* arg, int N, int H, int W, int C, int ph, int pw,
-                              int sh, int sw, int pad_t, int pad_l, int Ho, int Wo, const uint16_t* x, const float* st,
-                              float* part, int T, hipStream_t s, long long* acc = nullptr, int acc_reps = 1);
-hipError_t pool_bn_bwd_apply(const uint16_t* dpool, const uint8_t* arg, int N, int H, int W, int C, int ph, int pw,
-                             int sh, int sw, int pad_t, int pad_l, int Ho, int Wo, const uint16_t* x, const float* st,
-                             const float* co, uint16_t* dx, hipStream_t s, const BNBwdFin* bf = nullptr);
+hipError_t pool_bn_bwd_reduce(const uint16_t* dpool, const uint8_t* arg, const PoolGeo& g, const uint16_t* x,
+                              const float* st, float* part, int T, hipStream_t s, long long* acc = nullptr,
+                              int acc_reps = 1);
+hipError_t pool_bn_bwd_apply(const uint16_t* dpool, const uint8_t* arg, const PoolGeo& g, const uint16_t* x,
+                             const float* st, const float* co, uint16_t* dx, hipStream_t s,
+                             const BNBwdFin* bf = nullptr);
 // global average pool over H*W: x [N][HW][C] bf16 -> y [N][C] (bf16 or fp32)
 hipError_t gap_fwd(const uint16_t* x, int N, int HW, int C, void* y, int y_f32, hipStream_t s);
 hipError_t gap_bwd(const void* dy, int dy_f32, int N, int HW, int C, uint16_t* dx, hipStream_t s);
@@ -106,11 +113,6 @@ hipError_t act_bwd(const uint16_t* dy, const uint16_t* y, uint16_t* dx, long n, 
 // same call with the same seed is the backward (dx from dy)
 hipError_t dropout(const uint16_t* x, uint16_t* y, long n, const Ctrl* ctrl, uint32_t seed, float rate,
                    hipStream_t s);
-// average pooling, divisor = in-bounds taps (TF 'same' semantics)
-hipError_t avgpool_fwd(const uint16_t* x, int N, int H, int W, int C, int ph, int pw, int sh, int sw, int pad_t,
-                       int pad_l, int Ho, int Wo, uint16_t* y, hipStream_t s);
-hipError_t avgpool_bwd(const uint16_t* dy, int N, int H, int W, int C, int ph, int pw, int sh, int sw, int pad_t,
-                       int pad_l, int Ho, int Wo, uint16_t* dx, hipStream_t s);
 // Inference: BN st rows from the moving statistics; this step's logits rows -> out at the
 // device cursor; fold the metric tail into ctrl (tail cleared) and advance the cursor
 hipError_t bn_infer_st(const float* rmean, const float* rvar, const float* gamma, const float* beta, float eps, int C,
@@ -155,7 +157,6 @@ hipError_t softmax_xent(const float* logits, int ld, const int32_t* labels, int 
 hipError_t softmax_xent_dense(const float* logits, int ld, const int32_t* labels, const float* targets, int B, int K,
                               float label_smoothing, float scale, const Ctrl* ctrl, uint16_t* dlogits, float* tail,
                               float* rows, hipStream_t s, float* bias_grad = nullptr);
-int colsum_splits(int M, int N);
 
 // Optimizer ---------------------------------------------------------------------------------
 // flat multi-tensor Keras SGD over the master buffer: P, V fp32 updated from G; Pb = bf16(P)
@@ -166,7 +167,6 @@ hipError_t sgd_flat(float* P, const float* G, float* V, uint16_t* Pb, long n, fl
 // from ctrl (lr / momentum / nesterov, so a new lr needs no re-capture); block 0 also
 // folds the step's metric tail [loss, correct, count] into the epoch accumulators and
 // advances ctrl->cursor / ctrl->iterations.
-struct Ctrl;
 hipError_t sgd_step(float* P, const float* G, float* V, uint16_t* Pb, long n, Ctrl* ctrl, const float* tail,
                     hipStream_t s);
 // kind 0 SGD (S0 momentum; flag = nesterov), 1 Adam (S0 m, S1 v, S2 vhat; flag = amsgrad),

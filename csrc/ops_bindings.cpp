@@ -22,6 +22,12 @@ T* P_(uintptr_t p) { return reinterpret_cast<T*>(p); }
 void check(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// the 12 ints of ops/hip.py pool_geo(), in PoolGeo's field order
+damd::PoolGeo geo_(const std::vector<int>& g) {
+  if (g.size() != 12) throw std::invalid_argument("pool geometry");
+  return damd::PoolGeo{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]};
+}
 }  // namespace
 
 namespace damd {
@@ -148,9 +154,9 @@ void register_kernel_ops(py::module_& m) {
                               P_<u16>(dz), P_<float>(part), T, M, C, P_<ihipStream_t>(s)),
           "bn_bwd_reduce");
   });
-  m.def("bn_bwd_finalize", [](U part, int T, int C, float count, U st, U gamma, U dgamma, U dbeta, U co, U s) {
-    check(damd::bn_bwd_finalize(P_<const float>(part), T, C, count, P_<const float>(st), P_<const float>(gamma),
-                                P_<float>(dgamma), P_<float>(dbeta), P_<float>(co), P_<ihipStream_t>(s)),
+  m.def("bn_bwd_finalize", [](U part, int T, int C, float count, U st, U dgamma, U dbeta, U co, U s) {
+    check(damd::bn_bwd_finalize(P_<const float>(part), T, C, count, P_<const float>(st), P_<float>(dgamma),
+                                P_<float>(dbeta), P_<float>(co), P_<ihipStream_t>(s)),
           "bn_bwd_finalize");
   });
   m.def("bn_bwd_apply", [](U dy, U y, int relu_mask, U x, U st, U co, U dx, long M, int C, U s) {
@@ -216,58 +222,45 @@ void register_kernel_ops(py::module_& m) {
   });
   m.def("bn_relu_maxpool_fwd_fin", [mkfin](U x, std::vector<int> g, U y, U arg, std::vector<U> p, std::vector<float> v,
                                            U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
+    const damd::PoolGeo geo = geo_(g);
     const damd::BNFin f = mkfin(p, v);
-    check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), f.st, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8],
-                                    g[9], g[10], g[11], P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s), &f),
+    check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), f.st, geo, P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s), &f),
           "bn_relu_maxpool_fwd_fin");
   });
   m.def("pool_bn_bwd_reduce_acc", [](U dpool, U arg, std::vector<int> g, U x, U st, U acc, int T, U s, int reps) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), g[0], g[1], g[2], g[3], g[4], g[5],
-                                   g[6], g[7], g[8], g[9], g[10], g[11], P_<const u16>(x), P_<const float>(st),
-                                   nullptr, T, P_<ihipStream_t>(s), P_<long long>(acc), reps),
+    check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
+                                   P_<const float>(st), nullptr, T, P_<ihipStream_t>(s), P_<long long>(acc), reps),
           "pool_bn_bwd_reduce_acc");
   });
   m.def("pool_bn_bwd_apply_fin", [mkbfin](U dpool, U arg, std::vector<int> g, U x, U st, U dx, std::vector<U> bp,
                                           float count, U s, int reps) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
+    const damd::PoolGeo geo = geo_(g);
     const damd::BNBwdFin f = mkbfin(bp, count, reps);
-    check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), g[0], g[1], g[2], g[3], g[4], g[5],
-                                  g[6], g[7], g[8], g[9], g[10], g[11], P_<const u16>(x), P_<const float>(st), f.co,
-                                  P_<u16>(dx), P_<ihipStream_t>(s), &f),
+    check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), geo, P_<const u16>(x),
+                                  P_<const float>(st), f.co, P_<u16>(dx), P_<ihipStream_t>(s), &f),
           "pool_bn_bwd_apply_fin");
   });
   m.def("maxpool_fwd", [](U x, std::vector<int> g, U y, U arg, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::maxpool_fwd(P_<const u16>(x), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10],
-                            g[11], P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s)),
+    check(damd::maxpool_fwd(P_<const u16>(x), geo_(g), P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s)),
           "maxpool_fwd");
   });
   m.def("maxpool_bwd", [](U dy, U arg, std::vector<int> g, U dx, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::maxpool_bwd(P_<const u16>(dy), P_<const uint8_t>(arg), g[0], g[1], g[2], g[3], g[4], g[5], g[6],
-                            g[7], g[8], g[9], g[10], g[11], P_<u16>(dx), P_<ihipStream_t>(s)),
+    check(damd::maxpool_bwd(P_<const u16>(dy), P_<const uint8_t>(arg), geo_(g), P_<u16>(dx), P_<ihipStream_t>(s)),
           "maxpool_bwd");
   });
   m.def("bn_relu_maxpool_fwd", [](U x, U st, std::vector<int> g, U y, U arg, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), P_<const float>(st), g[0], g[1], g[2], g[3], g[4], g[5], g[6],
-                                    g[7], g[8], g[9], g[10], g[11], P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s)),
+    check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), P_<const float>(st), geo_(g), P_<u16>(y), P_<uint8_t>(arg),
+                                    P_<ihipStream_t>(s)),
           "bn_relu_maxpool_fwd");
   });
   m.def("pool_bn_bwd_reduce", [](U dpool, U arg, std::vector<int> g, U x, U st, U part, int T, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), g[0], g[1], g[2], g[3], g[4], g[5],
-                                   g[6], g[7], g[8], g[9], g[10], g[11], P_<const u16>(x), P_<const float>(st),
-                                   P_<float>(part), T, P_<ihipStream_t>(s)),
+    check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
+                                   P_<const float>(st), P_<float>(part), T, P_<ihipStream_t>(s)),
           "pool_bn_bwd_reduce");
   });
   m.def("pool_bn_bwd_apply", [](U dpool, U arg, std::vector<int> g, U x, U st, U co, U dx, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), g[0], g[1], g[2], g[3], g[4], g[5],
-                                  g[6], g[7], g[8], g[9], g[10], g[11], P_<const u16>(x), P_<const float>(st),
-                                  P_<const float>(co), P_<u16>(dx), P_<ihipStream_t>(s)),
+    check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
+                                  P_<const float>(st), P_<const float>(co), P_<u16>(dx), P_<ihipStream_t>(s)),
           "pool_bn_bwd_apply");
   });
   m.def("gap_fwd", [](U x, int N, int HW, int C, U y, int y_f32, U s) {
@@ -290,16 +283,10 @@ void register_kernel_ops(py::module_& m) {
           "dropout");
   });
   m.def("avgpool_fwd", [](U x, std::vector<int> g, U y, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::avgpool_fwd(P_<const u16>(x), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10],
-                            g[11], P_<u16>(y), P_<ihipStream_t>(s)),
-          "avgpool_fwd");
+    check(damd::avgpool_fwd(P_<const u16>(x), geo_(g), P_<u16>(y), P_<ihipStream_t>(s)), "avgpool_fwd");
   });
   m.def("avgpool_bwd", [](U dy, std::vector<int> g, U dx, U s) {
-    if (g.size() != 12) throw std::invalid_argument("pool geometry");
-    check(damd::avgpool_bwd(P_<const u16>(dy), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10],
-                            g[11], P_<u16>(dx), P_<ihipStream_t>(s)),
-          "avgpool_bwd");
+    check(damd::avgpool_bwd(P_<const u16>(dy), geo_(g), P_<u16>(dx), P_<ihipStream_t>(s)), "avgpool_bwd");
   });
   m.def("bn_infer_st", [](U rmean, U rvar, U gamma, U beta, float eps, int C, U st, U s) {
     check(damd::bn_infer_st(P_<const float>(rmean), P_<const float>(rvar), P_<const float>(gamma),

@@ -734,7 +734,7 @@ class NativeGraphEngine(Engine):
                 r.attrs["dead"] = True
                 self._alias(r.out, y)
                 # BN -> ReLU -> MaxPool (the ResNet stem): the pool normalises on the fly and
-                # the BN+ReLU output is never stored (layer_ops.hip stem fusion)
+                # the BN+ReLU output is never stored (pool.hip stem fusion)
                 outs = r.out.consumers
                 if (len(outs) == 1 and outs[0].kind == "MaxPooling2D"
                         and env.get_bool("DAMD_STEM_FUSE", True)):
@@ -1384,9 +1384,11 @@ class NativeGraphEngine(Engine):
         fin = nd.attrs.get("fin")
         if fin is not None:
             if not nd.attrs.get("stats_from_conv"):  # sum / sum of squares of x into acc_f
+                # (bn_bwd_reduce adds two words per value, replicas 4C apart: the layout it is
+                # checked against here)
                 self.C.bn_bwd_reduce_acc(x.buf.data_ptr(), 0, 0, x.buf.data_ptr(), self._ident(C).data_ptr(), 0,
                                          nd.attrs["acc_f"].data_ptr(), nd.attrs["T"], M, C, H.stream_handle(),
-                                         H.acc_reps(nd.attrs["acc_f"]))
+                                         H.acc_reps(nd.attrs["acc_f"], C, 4))
             if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None or nd.attrs.get("conv_fold"):
                 return  # finalized and applied by the fused Add / MaxPool / direct conv that consumes it
             H.bn_apply_fin(x.buf, nd.out.root().buf, fin, relu=nd.attrs.get("relu", False))
@@ -1572,7 +1574,7 @@ class NativeGraphEngine(Engine):
         else:
             C_.bn_bwd_reduce(dy.data_ptr(), ym, mode, x.buf.data_ptr(), st.data_ptr(),
                              dz_out.data_ptr() if (dz_out is not None and relu) else 0, part.data_ptr(), Tn, M, C, s)
-        C_.bn_bwd_finalize(part.data_ptr(), Tn, C, float(M), st.data_ptr(), 0,
+        C_.bn_bwd_finalize(part.data_ptr(), Tn, C, float(M), st.data_ptr(),
                            self.gviews[id(l.gamma)].data_ptr() if l.gamma is not None else 0,
                            self.gviews[id(l.beta)].data_ptr() if l.beta is not None else 0, co.data_ptr(), s)
         if dx is not None:

@@ -1,5 +1,5 @@
-"""Python launchers for the generic-path HIP kernels (csrc/kernels/gemm.hip,
-csrc/kernels/layer_ops.hip).
+"""Python launchers for the generic-path HIP kernels (csrc/kernels/: gemm.hip and the conv
+kernels; bn.hip, pool.hip, loss_head.hip, optimizer.hip, glue.hip, augment.hip).
 
 These are thin, validating wrappers: they check dtypes, shapes, contiguity and the
 16-byte alignment the kernels' vector accesses assume, pick the tile shape and split-K
@@ -247,16 +247,22 @@ def _wgrad_gemm(A, B, dw, workspace, *, amode, M, N, K, lda=0, ldb=0, geo=(), ac
     _C().splitk_reduce(_ptr(workspace), splits, M * N, _ptr(dw), stream_handle(), accumulate=int(accumulate))
 
 
-def acc_reps(acc):
-    """Replica count of a BatchNorm statistics accumulator (int64 fixed point, layer_ops.h
-    BNFin): [reps + 1, 2C] forward / [reps + 1, 4C] backward (2-D: the last row is the sticky
-    non-finite flag plane, damd_common.h bnacc_flag) or one replica + its flag plane (1-D,
-    [2 x K]).  Producer block b adds into replica b % reps."""
-    if acc is None or acc.dim() != 2:
+def acc_reps(acc, C: int, words: int) -> int:
+    """Replica count of a BatchNorm statistics accumulator of C channels (int64 fixed point,
+    layer_ops.h BNFin / BNBwdFin), after checking its layout: ``words`` per channel (2 forward,
+    4 backward) in [reps + 1, words C] (2-D: the last row is the sticky non-finite flag plane,
+    damd_common.h bnacc_flag) or one replica + its flag plane (1-D, [2 words C]).  Producer
+    block b adds into replica b % reps, and every kernel writes the flag plane behind the last
+    replica: a tensor without it would be written past its end, so this raises instead."""
+    if acc.dtype != torch.int64 or not acc.is_contiguous():
+        raise ValueError("a BatchNorm accumulator is a contiguous int64 tensor")
+    K = words * C
+    if acc.dim() == 2 and acc.shape[0] >= 2 and acc.shape[1] == K:
+        return int(acc.shape[0]) - 1
+    if acc.dim() == 1 and acc.numel() == 2 * K:
         return 1
-    if acc.shape[0] < 2:
-        raise ValueError("a BatchNorm accumulator needs >= 1 replica row + the flag row")
-    return int(acc.shape[0]) - 1
+    raise ValueError(f"a BatchNorm accumulator is [reps + 1, {K}] (replicas + the flag row) or [{2 * K}], "
+                     f"got {tuple(acc.shape)}")
 
 
 def acc_zeros(reps: int, K: int, device) -> torch.Tensor:
@@ -308,15 +314,15 @@ def bn_acc_decode(acc: torch.Tensor, words: int = 1) -> torch.Tensor:
     return out
 
 
-def _stats_ptrs(stats):
-    """(partials pointer, accumulator pointer, replicas) of a stats argument: an fp32
-    [T][2][N] partials tensor, or an int64 fixed-point accumulator [2N] / [reps, 2N]
-    (forward) or [reps, 4N] (backward, E_BNRED) (BNFin: producers add, the consumer
+def _stats_ptrs(stats, N, words=2):
+    """(partials pointer, accumulator pointer, replicas) of a stats argument over N columns:
+    an fp32 [T][2][N] partials tensor, or an int64 fixed-point accumulator (acc_reps) of 2
+    words per column (forward) or 4 (backward, E_BNRED) (BNFin: producers add, the consumer
     finalizes)."""
     if stats is None:
         return 0, 0, 1
     if stats.dtype == torch.int64:
-        return 0, _ptr(stats), acc_reps(stats)
+        return 0, _ptr(stats), acc_reps(stats, N, words)
     return _ptr(stats), 0, 1
 
 
@@ -325,7 +331,7 @@ def gemm(A, B, C, *, amode, bmode, M, N, K, lda=0, ldb=0, ldc=0, epi=0, bias=Non
          bnin=None, slab=None):
     t = pick_tile(N) if tile is None else tile
     kps = k_per_split if k_per_split is not None else -(-K // BK) * BK
-    sp, sa, reps = _stats_ptrs(stats)
+    sp, sa, reps = _stats_ptrs(stats, N, 4 if epi & E_BNRED else 2)
     bp, bv = bnin[0].args() if bnin is not None else ([], [])
     _C().gemm(amode, bmode, epi, splits, t, _ptr(A), _ptr(B), _ptr(C), _ptr(bias), sp, _ptr(R), M, N, K,
               lda, ldb, ldc, list(geo), kc, kps, stream_handle(), kstep, stats_acc=sa, bnx=_ptr(bnx), bnst=_ptr(bnst),
@@ -502,7 +508,7 @@ def conv_fwd_stem4(x, w8, out, kernel_size, strides=(2, 2), padding="same", bias
     ws = _workspace(workspace, plan["ws"], x.device)
     gemm(x, w8, ws, amode=A_CONV64, bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=E_SLAB,
          splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=32)
-    sp, sa, reps = _stats_ptrs(stats)
+    sp, sa, reps = _stats_ptrs(stats, cout)
     _C().splitk_finish(_ptr(ws), plan["splits"], M, cout, _ptr(bias), 0, int(relu), sp, FINISH_RB,
                        _ptr(out), cout, stream_handle(), stats_acc=sa, stats_reps=reps)
 
@@ -511,11 +517,7 @@ def _check_stats(stats, plan, cout, who):
     if stats is None:
         return
     if stats.dtype == torch.int64:
-        ok = (stats.numel() == 4 * cout if stats.dim() == 1 else
-              (stats.dim() == 2 and stats.shape[0] >= 2 and stats.shape[-1] == 2 * cout))
-        if not ok:
-            raise ValueError(f"{who}: a statistics accumulator is int64 [reps + 1][2 x {cout}], "
-                             f"got {tuple(stats.shape)}")
+        acc_reps(stats, cout, 2)
     elif stats.shape[0] != plan["stats_T"]:
         raise ValueError(f"{who}: stats needs {plan['stats_T']} partial rows, got {stats.shape[0]}")
 
@@ -659,7 +661,7 @@ def conv_fwd(x, w, out, strides=(1, 1), padding="valid", bias=None, relu=False, 
             return
     gemm(x, w, ws, amode=plan["amode"], bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=E_SLAB,
          splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo)
-    sp, sa, reps = _stats_ptrs(stats)
+    sp, sa, reps = _stats_ptrs(stats, cout)
     _C().splitk_finish(_ptr(ws), plan["splits"], M, cout, _ptr(bias), 0, int(relu), sp, FINISH_RB,
                        _ptr(out), cout, stream_handle(), stats_acc=sa, stats_reps=reps)
 
@@ -700,8 +702,8 @@ def conv_dgrad(dy, w, dx, strides=(1, 1), padding="valid", accumulate=False,
     (x, st, part): dx is the gradient of relu(BN(x)) (BN coefficients st [4][Cin]); when the
     direct kernel runs (conv_dgrad_plan stats_T rows) it also writes the BN-backward
     partials (sum dz, sum dz * xhat per tile) into part [stats_T][2][Cin] (or adds them into
-    an int64 fixed-point accumulator [reps][4 Cin]: two words per value), replacing
-    bn_bwd_reduce.  Returns True when it did."""
+    an int64 fixed-point accumulator [reps + 1][4 Cin]: two words per value, then the flag
+    row; acc_reps), replacing bn_bwd_reduce.  Returns True when it did."""
     n, h, wd, cin, ho, wo, kh, kw, s, pad, cout = conv_geo(dx.shape, w.shape, strides, padding)
     if s not in (1, 2):
         raise ValueError("conv_dgrad: stride 1 or 2")
@@ -715,10 +717,12 @@ def conv_dgrad(dy, w, dx, strides=(1, 1), padding="valid", accumulate=False,
     geo = (h, wd, cout, ho, wo, kh, kw, s, pad)
     if bnred is not None and plan["amode"] == A_DGRAD3 and not accumulate:
         bx, bst, part = bnred
-        is_acc = part.dtype == torch.int64  # a fixed-point accumulator [reps][4 Cin] (BNBwdFin)
-        if ((part.shape[-1] != 4 * cin if is_acc else part.shape[0] != plan["stats_T"])
-                or tuple(bx.shape) != tuple(dx.shape)):
-            raise ValueError("conv_dgrad: bnred partials / BN input do not match the plan")
+        if part.dtype == torch.int64:  # a fixed-point accumulator (BNBwdFin)
+            acc_reps(part, cin, 4)
+        elif part.shape[0] != plan["stats_T"]:
+            raise ValueError("conv_dgrad: bnred partials do not match the plan")
+        if tuple(bx.shape) != tuple(dx.shape):
+            raise ValueError("conv_dgrad: bnred BN input does not match dx")
         gemm(dy, w, dx, amode=A_DGRAD3, bmode=B_KC, M=M, N=cin, K=K, ldc=cin, epi=E_BF16 | E_BNRED, kc=cout,
              geo=geo, stats=part, tile=plan["tile"], bnx=bx, bnst=bst)
         return True
@@ -791,7 +795,7 @@ def bn_bwd(dy, y, relu_mask, x, st, part, co, dx, dgamma=None, dbeta=None, dz_ou
     assert part.numel() >= T * 2 * C
     s = stream_handle()
     _C().bn_bwd_reduce(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dz_out), _ptr(part), T, M, C, s)
-    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), 0, _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
+    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
     _C().bn_bwd_apply(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(co), _ptr(dx), M, C, s)
 
 
@@ -832,7 +836,7 @@ def pool_bn_bwd(dpool, arg, x, st, part, co, dx, pool, strides, padding, dgamma=
     assert part.numel() >= T * 2 * C
     s = stream_handle()
     _C().pool_bn_bwd_reduce(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(part), T, s)
-    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), 0, _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
+    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
     if dx is not None:
         _C().pool_bn_bwd_apply(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(co), _ptr(dx), s)
 
@@ -840,7 +844,7 @@ def pool_bn_bwd(dpool, arg, x, st, part, co, dx, pool, strides, padding, dgamma=
 # ---- BatchNorm with the finalize folded into the consumer kernel (layer_ops.h BNFin) ------
 # The producers (conv / dense GEMM epilogue with an int64 `stats` accumulator, split-K
 # finish, bn_bwd_reduce with `acc`) add their per-block partials into an int64 fixed-point
-# accumulator ([2C] / [reps, 2C] forward, [reps, 4C] backward: block b into replica
+# accumulator ([reps + 1, 2C] forward, [reps + 1, 4C] backward, acc_reps: block b into replica
 # b % reps; integer sums, so the statistics do not depend on the blocks' arrival order);
 # the consumer derives the coefficients in its prologue, so neither bn_finalize nor
 # bn_bwd_finalize is launched.  The accumulators must be zero before the producers run
@@ -849,15 +853,22 @@ FIN_MAX_C = 4096
 
 
 class BNFin:
-    """Forward finalize parameters of one BatchNorm: int64 accumulator acc [2][C] (sum,
-    sum of squares of the BN input), gamma / beta (None: 1 / 0), st [4][C] written by the
-    consumer's block 0 (mean, invstd, scale, shift), moving statistics (None: not
-    updated), the element count per channel, epsilon and the moving-average momentum."""
+    """Forward finalize parameters of one BatchNorm: int64 accumulator acc [reps + 1][2 C]
+    (per replica the sums, then the sums of squares of the BN input; the last row is the flag
+    plane; acc_reps) or None (the consumer reads st), gamma / beta (None: 1 / 0), st [4][C]
+    written by the consumer's block 0 (mean, invstd, scale, shift), moving statistics (None:
+    not updated), the element count per channel, epsilon and the moving-average momentum."""
 
     def __init__(self, acc, gamma, beta, st, rmean, rvar, count, eps, momentum):
         self.acc, self.st = acc, st
+        if acc is None:
+            reps = 1
+        elif st is None:
+            raise ValueError("BNFin: an accumulator needs st [4][C] to finalize into")
+        else:
+            reps = acc_reps(acc, st.numel() // 4, 2)
         self._p = [_ptr(acc), _ptr(gamma), _ptr(beta), _ptr(st), _ptr(rmean), _ptr(rvar)]
-        self._v = [float(count), float(eps), float(momentum), float(acc_reps(acc))]
+        self._v = [float(count), float(eps), float(momentum), float(reps)]
 
     def args(self):
         return self._p, self._v
@@ -878,13 +889,14 @@ def bn_apply_fin(x, y, fin: BNFin, relu=False, r=None, fin2: Optional[BNFin] = N
 
 def bn_bwd_fin(dy, y, relu_mask, x, st, acc, co, dx, dgamma=None, dbeta=None, dz_out=None, reduce=True):
     """BN backward in two launches: bn_bwd_reduce adds sum(dz), sum(dz * xhat) into the int64
-    accumulator acc [reps][4C] (two words per value; reduce=False: a conv epilogue, E_BNRED, already did); bn_bwd_apply
-    derives co, adds dgamma / dbeta (block 0) and writes dx."""
+    accumulator acc [reps + 1][4C] (two words per value, then the flag row; reduce=False: a conv
+    epilogue, E_BNRED, already did); bn_bwd_apply derives co, adds dgamma / dbeta (block 0) and
+    writes dx."""
     C = x.shape[-1]
     M = x.numel() // C
+    r = acc_reps(acc, C, 4)
     T = _C().bn_bwd_blocks(M, C)
     s = stream_handle()
-    r = acc_reps(acc)
     if reduce:
         _C().bn_bwd_reduce_acc(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dz_out), _ptr(acc), T, M, C,
                                s, r)
@@ -904,11 +916,11 @@ def bn_bwd_fin_dual(dy, y, relu_mask, bns):
     a, b = bns
     C = a["x"].shape[-1]
     M = a["x"].numel() // C
-    if b["x"].shape != a["x"].shape or acc_reps(a["acc"]) != acc_reps(b["acc"]) or relu_mask not in (0, 1):
+    r = acc_reps(a["acc"], C, 4)
+    if b["x"].shape != a["x"].shape or acc_reps(b["acc"], C, 4) != r or relu_mask not in (0, 1):
         raise ValueError("bn_bwd_fin_dual: the two BatchNorms must match in shape and replicas")
     T = _C().bn_bwd_blocks(M, C)
     s = stream_handle()
-    r = acc_reps(a["acc"])
     _C().bn_bwd_reduce_dual_acc(_ptr(dy), _ptr(y), int(relu_mask), _ptr(a["x"]), _ptr(b["x"]), _ptr(a["st"]),
                                 _ptr(b["st"]), _ptr(a["acc"]), _ptr(b["acc"]), T, M, C, s, r)
     _C().bn_bwd_apply_dual_fin(_ptr(dy), _ptr(y), int(relu_mask), _ptr(a["x"]), _ptr(b["x"]), _ptr(a["st"]),
@@ -928,9 +940,9 @@ def pool_bn_bwd_fin(dpool, arg, x, st, acc, co, dx, pool, strides, padding, dgam
     g = pool_geo(x.shape, pool, strides, padding)
     C = x.shape[-1]
     M = x.numel() // C
+    r = acc_reps(acc, C, 4)
     T = _C().bn_bwd_blocks(M, C)
     s = stream_handle()
-    r = acc_reps(acc)
     _C().pool_bn_bwd_reduce_acc(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(acc), T, s, r)
     _C().pool_bn_bwd_apply_fin(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(dx),
                                [_ptr(acc), _ptr(dgamma), _ptr(dbeta), _ptr(co)], float(M), s, r)

@@ -158,7 +158,7 @@ def clip_grad(g, table, mode, c):
 
 
 def lr_schedule32(schedule, step) -> float:
-    """The fp32 host mirror of opt_step's device-side learning-rate schedule (layer_ops.hip
+    """The fp32 host mirror of opt_step's device-side learning-rate schedule (optimizer.hip
     lr_eval): one of the five keras/schedules.py classes at the integer ``step``, the same
     operations in the same order in ``numpy.float32``, all step logic in integers.  Returns
     the float32 as a Python float."""

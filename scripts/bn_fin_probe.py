@@ -51,7 +51,7 @@ for (hw, c) in [(56, 64), (28, 128), (14, 256), (7, 512)]:
 
     def bwd_base():
         C_.bn_bwd_reduce(dy.data_ptr(), 0, 2, x.data_ptr(), st.data_ptr(), 0, part.data_ptr(), T, M, c, s)
-        C_.bn_bwd_finalize(part.data_ptr(), T, c, float(M), st.data_ptr(), 0, 0, 0, co.data_ptr(), s)
+        C_.bn_bwd_finalize(part.data_ptr(), T, c, float(M), st.data_ptr(), 0, 0, co.data_ptr(), s)
         C_.bn_bwd_apply(dy.data_ptr(), 0, 2, x.data_ptr(), st.data_ptr(), co.data_ptr(), out.data_ptr(), M, c, s)
 
     tb, tbb = timeit(base), timeit(bwd_base)

@@ -1,5 +1,5 @@
-"""The batch gather, layout and inference glue kernels of csrc/kernels/layer_ops.hip, called
-directly: gather_batch (its three code paths, zero ranges, folded PadCastJob, Ctrl::cur3),
+"""The batch gather, layout and inference glue kernels of csrc/kernels/ (glue.hip,
+loss_head.hip, optimizer.hip, bn.hip), called directly: gather_batch (its three code paths, zero ranges, folded PadCastJob, Ctrl::cur3),
 pad_cast / unpad_add, logits_store / step_fold / bn_infer_st, add_bf16 / relu_bwd, the
 casts and sgd_step.
 

@@ -1,4 +1,4 @@
-"""Numerics of the generic-path HIP kernels (csrc/kernels/gemm.hip, layer_ops.hip)
+"""Numerics of the generic-path HIP kernels (csrc/kernels/gemm.hip, bn.hip, pool.hip, loss_head.hip, optimizer.hip, glue.hip)
 against plain PyTorch fp32 references of the same ops (distributed_amd/ops/reference.py).
 
 bf16 operands are rounded once and then fed to BOTH sides, so the only differences are
