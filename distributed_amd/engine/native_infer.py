@@ -24,7 +24,6 @@ Plans are cached per (model, batch size); weights are re-read at the start of ev
 """
 from __future__ import annotations
 
-import gc
 from typing import Dict, Tuple
 
 import numpy as np
@@ -32,22 +31,21 @@ import torch
 
 from ..ops import hip as H
 from ..utils import logging as dlog
-from .native_graph import (C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, NativeGraphEngine, _i2f,
-                           _layer_graph, _pad8, _param_weights, dense_targets, loss_head_ok, output_head,
-                           reg_rows, regularizers_ok)
+from .native_exec import PlanExec, capture
+from .native_graph import C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, _i2f
+from .native_params import FlatParams
+from .native_plan import (_layer_graph, _param_weights, dense_targets, layers_eligible, loss_head_ok, lower,
+                          output_head, regularizers_ok)
 
 
-class NativeInference(NativeGraphEngine):
+class NativeInference:
     name = "native_infer"
-    _weights_static = True
-    _bn_fin = False  # BN runs from the moving statistics (bn_infer_st)
-    _aug_training = False  # an input prefix runs with flips off and crops centred
 
     @staticmethod
     def eligible(model, device, evaluate: bool = False) -> Tuple[bool, str]:
         if torch.device(device).type != "cuda":
             return False, "not on a GPU"
-        ok, why = NativeGraphEngine.layers_eligible(model)
+        ok, why = layers_eligible(model)
         if ok and evaluate:  # (predict uses no loss: its eligibility is the layers' alone)
             ok, why = regularizers_ok(model)
             if not ok:
@@ -56,57 +54,36 @@ class NativeInference(NativeGraphEngine):
         return ok, why
 
     def __init__(self, model, batch: int, device):
-        # no Engine.__init__: an inference plan owns no strategy, gradients or optimizer
+        # an inference plan owns no strategy, gradients or optimizer: the forward-only plan,
+        # a copy of every weight it reads, and the plan's buffers and forward ops
         from ..native import require_C
 
         self.model, self.B, self.device = model, int(batch), torch.device(device)
         self.C = require_C()
-        self.rank = 0
-        self._build()
-        for nd in self.nodes:
-            if nd.kind == "Dropout" and not nd.attrs.get("dead"):
-                nd.attrs["dead"] = True  # identity at inference
-                self._alias(nd.out, nd.inputs[0])
-            nd.attrs.pop("stats", None)  # BN uses the moving statistics: no batch statistics
-            nd.attrs.pop("stats_from_conv", None)
-        for t in self._all_tensors():
-            t.needs_grad = False
-        self._allocate()
         dev = self.device
-        # every weight the forward reads, frozen layers included (not only trainable_weights)
-        self.vars = _param_weights(model)
-        self.sizes = [int(np.prod(v.shape)) for v in self.vars]
-        offs, off = [], 0
-        for sz in self.sizes:
-            offs.append(off)
-            off = _pad8(off + sz)
-        self.nparam = off
-        self.offsets = offs
-        self.P = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.Pb = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        self.views, self.bviews = {}, {}
-        for v, sz, o in zip(self.vars, self.sizes, offs):
-            self.views[id(v)] = self.P[o:o + sz].view(v.shape)
-            self.bviews[id(v)] = self.Pb[o:o + sz].view(v.shape)
-        # weight regularizers (evaluate): R from one reg_penalty launch per call
-        rows = reg_rows(self.vars, offs)
-        self.reg_tab = H.reg_table(rows, dev) if rows else None
-        self.reg_scratch = H.reg_scratch(off, dev) if rows else None
+        self.plan = lower(model, self.B, inference=True)
+        # every weight the forward reads, frozen layers included (not only trainable_weights);
+        # its regularizer table (evaluate): R from one reg_penalty launch per call
+        self.params = FlatParams(_param_weights(model), dev)
+        # BN runs from the moving statistics (bn_infer_st), the padded weight copies are made
+        # once per call, an input prefix runs with flips off and crops centred
+        self.ex = PlanExec(self.plan, self.params, self.C, dev, bn_fin=False, weights_static=True,
+                           aug_training=False)
+        self.nodes, self.in_shape, self.K, self.ctrl = self.plan.nodes, self.plan.in_shape, self.ex.K, self.ex.ctrl
         self.tail = torch.zeros(8, dtype=torch.float32, device=dev)
-        self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._bufs: Dict[str, torch.Tensor] = {}
-        self._bn = [nd for nd in self.nodes if nd.kind == "BatchNormalization" and not nd.attrs.get("dead")]
+        self._bn = [nd for nd in self.plan.live if nd.kind == "BatchNormalization"]
         self._stream = torch.cuda.Stream(dev)
 
     # --- weights --------------------------------------------------------------------------
     def _refresh_weights(self):
-        for v in self.vars:
-            self.views[id(v)].copy_(v.value.detach().reshape(v.shape))
-        H.cast_bf16(self.P, self.Pb)
-        for nd in self.nodes:
-            if not nd.attrs.get("dead"):
-                self._pad_weights(nd)
+        p = self.params
+        for v in p.vars:
+            p.view(v).copy_(v.value.detach().reshape(v.shape))
+        H.cast_bf16(p.P, p.Pb)
+        for nd in self.plan.live:
+            self.ex.pad_weights(nd)
         keep = []  # moving statistics moved to the device for this call: alive until the sync
         for nd in self._bn:
             l = nd.layer
@@ -114,46 +91,36 @@ class NativeInference(NativeGraphEngine):
             mean, var = (w.value.detach().to(self.device, torch.float32).contiguous()
                          for w in (l.moving_mean, l.moving_variance))
             keep += [mean, var]
-            g = self.views[id(l.gamma)] if l.gamma is not None else None
-            b = self.views[id(l.beta)] if l.beta is not None else None
-            self.C.bn_infer_st(mean.data_ptr(), var.data_ptr(), g.data_ptr() if g is not None else 0,
-                               b.data_ptr() if b is not None else 0, float(l.epsilon), C, nd.attrs["st"].data_ptr(),
-                               H.stream_handle())
+            self.C.bn_infer_st(mean.data_ptr(), var.data_ptr(), H._ptr(p.view(l.gamma)), H._ptr(p.view(l.beta)),
+                               float(l.epsilon), C, nd.attrs["st"].data_ptr(), H.stream_handle())
         torch.cuda.current_stream(self.device).synchronize()
 
     # --- the step ---------------------------------------------------------------------------
-    def _fwd_BatchNormalization(self, nd):
-        if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None:
-            return  # applied by the fused Add / MaxPool that consumes it
-        H.bn_apply(nd.inputs[0].root().buf, nd.attrs["st"], nd.out.root().buf, relu=nd.attrs.get("relu", False))
-
     def _infer_step(self, mode: str):
-        C, B = self.C, self.B
+        C, B, ex = self.C, self.B, self.ex
         s = H.stream_handle()
         h, w, c = self.in_shape
         x, y = self._bufs["x"], self._bufs["y"]
         # uint8 inputs are fed as their raw values (Keras casts them), scale 1
         C.gather_batch(x.data_ptr(), int(x.dtype == torch.uint8), 1.0, y.data_ptr(), self.ctrl.data_ptr(), B,
-                       h * w, c, self.cin_pad, self.x0.buf.data_ptr(), self.labels.data_ptr(), s)
-        for nd in self.nodes:
-            if not nd.attrs.get("dead"):
-                getattr(self, "_fwd_" + nd.kind)(nd)
+                       h * w, c, self.plan.cin_pad, self.plan.x0.buf.data_ptr(), ex.labels.data_ptr(), s)
+        ex.forward()
         if mode == "predict":
-            if self.head_kind == "probs":  # the model's output is the softmax of the logits
-                H.softmax_store(self.logits, self.K, self.ctrl, self._bufs["out"])
+            if self.plan.head_kind == "probs":  # the model's output is the softmax of the logits
+                H.softmax_store(ex.logits, self.K, self.ctrl, self._bufs["out"])
             else:
-                C.logits_store(self.logits.data_ptr(), self.Kp, self.K, B, self.ctrl.data_ptr(),
+                C.logits_store(ex.logits.data_ptr(), ex.Kp, self.K, B, self.ctrl.data_ptr(),
                                self._bufs["out"].data_ptr(), s)
             C.step_fold(self.ctrl.data_ptr(), 0, s)
         elif mode == "evaluate_dense":
             # y: all-zero ids (gather_batch turns them into the 0 / -1 row validity); the
             # [n, K] target rows are read in place at the device cursor
-            H.softmax_xent_dense(self.logits, self._bufs["yd"], self.K, 1.0 / B, self.dlogits, self.tail,
-                                 label_smoothing=self._eps, labels=self.labels, ctrl=self.ctrl, rows=self.xent_rows)
+            H.softmax_xent_dense(ex.logits, self._bufs["yd"], self.K, 1.0 / B, ex.dlogits, self.tail,
+                                 label_smoothing=self._eps, labels=ex.labels, ctrl=self.ctrl, rows=ex.xent_rows)
             C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
         else:
-            H.softmax_xent(self.logits, self.labels, self.K, 1.0 / B, self.dlogits, self.tail, ctrl=self.ctrl,
-                           rows=self.xent_rows)
+            H.softmax_xent(ex.logits, ex.labels, self.K, 1.0 / B, ex.dlogits, self.tail, ctrl=self.ctrl,
+                           rows=ex.xent_rows)
             C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
 
     def _stage(self, x, y=None, dense=False):
@@ -214,17 +181,7 @@ class NativeInference(NativeGraphEngine):
             self._ctrl_reset(n)
             g = self._graphs.get(mode)
             if g is None:
-                g = torch.cuda.CUDAGraph()
-                gc.collect()
-                was = gc.isenabled()
-                gc.disable()
-                try:
-                    with torch.cuda.graph(g, stream=self._stream):
-                        self._infer_step(mode)
-                finally:
-                    if was:
-                        gc.enable()
-                self._graphs[mode] = g
+                g = self._graphs[mode] = capture(dev, lambda: self._infer_step(mode), stream=self._stream)
             for _ in range(steps):
                 g.replay()
         torch.cuda.synchronize(dev)
@@ -253,11 +210,12 @@ class NativeInference(NativeGraphEngine):
         self._run("evaluate_dense" if dense else "evaluate", n)
         c = self.ctrl.cpu().tolist()
         loss, cnt = _i2f(c[C_AL]), _i2f(c[C_AN])
-        if self.reg_tab is not None:
+        p = self.params
+        if p.reg_tab is not None:
             # the weights are static during the call: every row's loss gains the same R
-            H.reg_penalty(self.P, self.reg_tab, self.reg_scratch)
+            H.reg_penalty(p.P, p.reg_tab, p.reg_scratch)
             torch.cuda.synchronize(self.device)
-            loss += float(self.reg_scratch[-1]) * cnt
+            loss += float(p.reg_scratch[-1]) * cnt
         return loss, cnt, _i2f(c[C_AC])
 
 

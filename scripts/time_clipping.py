@@ -87,7 +87,7 @@ def time_kernels(launches, rounds, warmup):
     """grad_norm (per variable / global, without / with coefficients) and reg_penalty over
     ResNet-18's flat buffer."""
     import distributed_amd as tf
-    from distributed_amd.engine.native_graph import _pad8, reg_rows
+    from distributed_amd.engine.native_plan import _pad8, reg_rows
     from distributed_amd.ops import hip as H
 
     dev = torch.device("cuda:0")

@@ -102,7 +102,7 @@ def _time(g, launches):
 def time_kernels(launches, rounds, warmup):
     """reg_penalty and opt_step (table on / off) over ResNet-18's flat buffer and table."""
     import distributed_amd as tf
-    from distributed_amd.engine.native_graph import _pad8, reg_rows
+    from distributed_amd.engine.native_plan import _pad8, reg_rows
     from distributed_amd.native import require_C
     from distributed_amd.ops import hip as H
 

@@ -2,6 +2,7 @@
 buckets for ResNet-18 (BASELINE.json config 4) and the reference CNN — no device needed."""
 from distributed_amd import keras
 from distributed_amd.engine.native_graph import NativeGraphEngine
+from distributed_amd.engine.native_plan import lower, plan_buckets
 from distributed_amd.models import mnist_cnn, resnet18
 
 
@@ -44,34 +45,80 @@ def test_mnist_plan():
 
 def test_gradient_buckets_tile_the_flat_buffer():
     import numpy as np
-    import torch
 
     keras.backend.clear_session()
     m = resnet18()
-    pl = NativeGraphEngine.plan_only(m, 8)
-    pl.vars = m.trainable_weights
-    pl.sizes = [int(np.prod(v.shape)) for v in pl.vars]
-    pl.offsets, off = [], 0
-    for sz in pl.sizes:
-        pl.offsets.append(off)
+    pl = lower(m, 8)
+    tvars = m.trainable_weights
+    sizes = [int(np.prod(v.shape)) for v in tvars]
+    offsets, off = [], 0
+    for sz in sizes:
+        offsets.append(off)
         off = -(-(off + sz) // 8) * 8
-    pl.G = torch.zeros(off + 8)
-    pl._plan_buckets(4.0)  # 4 MB buckets over 46.8 MB of grads
-    bs = pl._buckets
+    bs, writes = plan_buckets(pl, tvars, sizes, offsets, off + 8, 4.0)  # 4 MB buckets over 46.8 MB of grads
     assert 5 <= len(bs) <= 16  # the 3x3x512x512 convs (9.4 MB) are buckets of their own
     assert bs[0]["hi"] == off + 8  # the first bucket (last layers) carries the metric tail
     covered = sorted((b["lo"], b["hi"]) for b in bs)
     assert covered[0][0] == 0 and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
     ids = [i for b in bs for i in b["vars"]]
-    assert sorted(ids) == sorted(id(v) for v in pl.vars)
+    assert sorted(ids) == sorted(id(v) for v in tvars)
     # every trainable variable has exactly one writer node in the backward plan
-    written = [i for vs in pl._writes.values() for i in vs]
-    assert sorted(written) == sorted(id(v) for v in pl.vars)
+    written = [i for vs in writes.values() for i in vs]
+    assert sorted(written) == sorted(id(v) for v in tvars)
     # the bucket of the first layers -- written last by backward, so its all-reduce trails
     # the step -- is cut at DAMD_BUCKET_LAST_MB (1 MB): a short exposed tail
     last = [b for b in bs if b["lo"] == 0][0]
     assert (last["hi"] - last["lo"]) * 4 <= 2**20, last["hi"] * 4
     assert bs[-1] is last
+
+
+def _bn_dropout_net():
+    L = keras.layers
+    return keras.Sequential([L.Conv2D(8, 3, use_bias=False, input_shape=(8, 8, 3)), L.BatchNormalization(), L.ReLU(),
+                             L.Dropout(0.5), L.Flatten(), L.Dense(10)])
+
+
+def _node_rows(pl, without=()):
+    return [(nd.kind, nd.layer.name, nd.out.shape, nd.attrs["dead"], sorted(nd.attrs),
+             {k: v for k, v in nd.attrs.items() if isinstance(v, (bool, int)) and k not in without})
+            for nd in pl.nodes]
+
+
+def test_inference_lowering_strips_training_only_work():
+    """lower(inference=True): Dropout is the identity, BatchNorm takes no batch statistics,
+    nothing needs a gradient -- decided in the lowering, on a plan of its own."""
+    keras.backend.clear_session()
+    inf = lower(_bn_dropout_net(), 2, inference=True)
+    before = _node_rows(inf)
+    drop = next(nd for nd in inf.nodes if nd.kind == "Dropout")
+    assert drop.attrs["dead"] and drop.out.alias_of is drop.inputs[0] and drop not in inf.live
+    assert not any("stats" in nd.attrs or "stats_from_conv" in nd.attrs for nd in inf.nodes)
+    assert not any(t.needs_grad for t in inf.all_tensors())
+    keras.backend.clear_session()
+    tr = lower(_bn_dropout_net(), 2)
+    kinds = {nd.kind: nd for nd in tr.nodes}
+    assert not kinds["Dropout"].attrs["dead"] and kinds["Dropout"].attrs["seed"] != 0
+    assert kinds["Dropout"] in tr.live and kinds["Dropout"].out.alias_of is None
+    assert kinds["Conv2D"].attrs["stats"] is True and kinds["BatchNormalization"].attrs["relu"] is True
+    assert kinds["BatchNormalization"].attrs["stats_from_conv"] is True
+    assert kinds["Conv2D"].out.needs_grad and not tr.x0.needs_grad
+    # two plans, no shared nodes or tensors: lowering one left the other as it was
+    assert tr is not inf and not {id(nd) for nd in tr.nodes} & {id(nd) for nd in inf.nodes}
+    assert not {id(t) for t in tr.all_tensors()} & {id(t) for t in inf.all_tensors()}
+    assert _node_rows(inf) == before
+
+
+def test_lowering_is_repeatable_and_rank_enters_only_the_dropout_seeds():
+    for build, batch in ((resnet18, 8), (_bn_dropout_net, 2)):
+        keras.backend.clear_session()
+        m = build()
+        a, b, r1 = lower(m, batch), lower(m, batch), lower(m, batch, rank=1)
+        assert _node_rows(a) == _node_rows(b)
+        assert _node_rows(a, without=("seed",)) == _node_rows(r1, without=("seed",))
+        assert (a.cin_pad, a.x0.shape, a.describe()) == (r1.cin_pad, r1.x0.shape, r1.describe())
+        drops = [i for i, nd in enumerate(a.nodes) if nd.kind == "Dropout"]
+        assert all(a.nodes[i].attrs["seed"] != r1.nodes[i].attrs["seed"] for i in drops)
+        assert bool(drops) == (build is _bn_dropout_net)
 
 
 class _FakeGPUStrategy:
