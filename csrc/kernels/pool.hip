@@ -690,7 +690,7 @@ hipError_t maxpool_fwd(const uint16_t* x, const PoolGeo& g, uint16_t* y, uint8_t
 }
 
 hipError_t maxpool_bwd(const uint16_t* dy, const uint8_t* arg, const PoolGeo& g, uint16_t* dx, hipStream_t s) {
-  if (g.C % 8) return hipErrorInvalidValue;
+  if (g.C % 8 || g.ph * g.pw > 255) return hipErrorInvalidValue;  // (tap codes are uint8, as the forward's)
   hipLaunchKernelGGL(maxpool_bwd_k, dim3(grid_for((long)g.N * g.H * g.W * g.C / 8)), dim3(NT), 0, s, dy, arg, g, dx);
   return hipGetLastError();
 }
@@ -729,7 +729,7 @@ hipError_t bn_relu_maxpool_fwd(const uint16_t* x, const float* st, const PoolGeo
 hipError_t pool_bn_bwd_reduce(const uint16_t* dpool, const uint8_t* arg, const PoolGeo& g, const uint16_t* x,
                               const float* st, float* part, int T, hipStream_t s, long long* acc, int acc_reps) {
   const int C = g.C;
-  if (C % 8 || C / 8 > NT || (!part && !acc) || acc_reps < 1) return hipErrorInvalidValue;
+  if (C % 8 || C / 8 > NT || g.ph * g.pw > 255 || (!part && !acc) || acc_reps < 1) return hipErrorInvalidValue;
   const long M = (long)g.N * g.H * g.W, rows = (M + T - 1) / T;
   if (quad_pool_geo(g)) {
     const long nq = (long)g.N * g.Ho * g.Wo, qpb = (nq + T - 1) / T;
@@ -746,7 +746,7 @@ hipError_t pool_bn_bwd_reduce(const uint16_t* dpool, const uint8_t* arg, const P
 hipError_t pool_bn_bwd_apply(const uint16_t* dpool, const uint8_t* arg, const PoolGeo& g, const uint16_t* x,
                              const float* st, const float* co, uint16_t* dx, hipStream_t s, const BNBwdFin* bfp) {
   const int C = g.C;
-  if (C % 8) return hipErrorInvalidValue;
+  if (C % 8 || g.ph * g.pw > 255) return hipErrorInvalidValue;
   const BNBwdFin f = bfp ? *bfp : kNoBwdFin;
   if (f.acc && (!f.co || C > FIN_MAX_C)) return hipErrorInvalidValue;
   const int cap = f.acc ? FIN_GRID_CAP : 8192;

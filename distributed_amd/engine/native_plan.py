@@ -452,9 +452,10 @@ class Plan:
                 r.attrs["dead"] = True
                 r.out.alias_of = y
                 # BN -> ReLU -> MaxPool (the ResNet stem): the pool normalises on the fly and
-                # the BN+ReLU output is never stored (pool.hip stem fusion)
+                # the BN+ReLU output is never stored (pool.hip stem fusion); its backward reduce
+                # holds one 8-channel group per thread, so wider layers keep the unfused pair
                 outs = r.out.consumers
-                if (len(outs) == 1 and outs[0].kind == "MaxPooling2D"
+                if (len(outs) == 1 and outs[0].kind == "MaxPooling2D" and y.shape[-1] <= H.STEM_FUSE_MAX_C
                         and env.get_bool("DAMD_STEM_FUSE", True)):
                     nd.attrs["pool"] = outs[0]
                     outs[0].attrs["bn"] = nd

@@ -850,6 +850,7 @@ def pool_bn_bwd(dpool, arg, x, st, part, co, dx, pool, strides, padding, dgamma=
 # bn_bwd_finalize is launched.  The accumulators must be zero before the producers run
 # (the native graph engine clears them all in the step's gather_batch launch).
 FIN_MAX_C = 4096
+STEM_FUSE_MAX_C = 2048  # pool.hip pool_bn_bwd_reduce: C / 8 channel groups within one 256-thread block
 
 
 class BNFin:

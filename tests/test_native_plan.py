@@ -170,6 +170,27 @@ def test_round3_layers_and_optimizers_are_native_eligible():
     assert pools[0].out.shape == (8, 7, 7, 16)
 
 
+def test_stem_fusion_stops_at_the_backward_reduce_channel_limit():
+    """BN -> ReLU -> MaxPool fuses into the pool (pool.hip) only up to the width its backward
+    reduce takes (C / 8 <= 256 threads: pool_bn_bwd_reduce refuses more at launch); a wider
+    stem keeps the unfused BN + pool pair and stays native."""
+    from distributed_amd.ops import hip as H
+
+    L = keras.layers
+    assert H.STEM_FUSE_MAX_C == 2048
+    for c, fused in ((H.STEM_FUSE_MAX_C, True), (H.STEM_FUSE_MAX_C + 8, False)):
+        keras.backend.clear_session()
+        m = keras.Sequential([L.Conv2D(c, 1, use_bias=False, input_shape=(4, 4, 8)), L.BatchNormalization(), L.ReLU(),
+                              L.MaxPooling2D(3, 2, padding="same"), L.Flatten(), L.Dense(16)])
+        pl = lower(m, 2)
+        bn = next(nd for nd in pl.nodes if nd.kind == "BatchNormalization")
+        pool = next(nd for nd in pl.nodes if nd.kind == "MaxPooling2D")
+        assert bn.attrs["relu"] and bn.out.shape == (2, 4, 4, c)
+        assert (bn.attrs.get("pool") is pool) == fused and (pool.attrs.get("bn") is bn) == fused, c
+        ok, why = NativeGraphEngine.eligible(_compiled(m, keras.optimizers.SGD(0.1)), _FakeGPUStrategy())
+        assert ok, why
+
+
 def test_direct_conv3_planner_on_resnet18_shapes():
     """The planner routes the ResNet-18 3x3/stride-1 convs of layers 1-3 (batch 64) to the
     direct kernel (conv3x3.hip) for forward and backprop-input, and keeps the implicit
