@@ -41,8 +41,6 @@ static_assert(NPARAM == kConvNetNParam && NGRAD == kConvNetNGrad, "param count")
 __host__ __device__ constexpr int kpitch(int pp) { return pp * 32 + 8; }
 __host__ __device__ constexpr int nsp(int ns) { return (ns + 3) & ~3; }
 
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ uint16_t bf16_lo(float v, uint16_t hi) { return f2bf(v - bf2f(hi)); }
 
 // next step index (wraps for benchmark epochs)
@@ -142,78 +140,121 @@ __device__ __forceinline__ void x_store(const XStage<U8>& st, float* xs, int lgi
 // argmax / ReLU mask match an fp32 conv; the 23 spare K slots of a 9-tap conv pay it.
 // Row tile rt = 4 pool windows x 4 sub-pixels (window wi = pl*64 + image), so the 4
 // pixels of one window are the 4 accumulator rows of one lane: bias + ReLU + max +
-// first-max argmax happen in registers.  Per-lane tap offsets / bit masks make the
-// hi/lo selection branch-free (a ?: on the value turns into divergent control flow that
-// serialises the LDS reads).
+// first-max argmax happen in registers.
+//
+// The conv phase is VALU-issue bound and at 12 waves each wave builds exactly one tile, so
+// whatever depends only on the lane, the wave or the slice is kept out of its stream:
+//   * the weight fragments lie in LDS in operand order (wf, conv_w_store): the thread that
+//     updates a weight splits it and stores the halves into the K slots that take them;
+//     conv_setup is two 16-byte reads and two bias reads per lane;
+//   * K slot 8 kg + j of lane group kg = lane >> 4 holds tap (j - kg) mod 9, so the 8 gather
+//     offsets and the hi / lo / zero choice of every slot depend on kg only: they are
+//     constants picked by kg (one byte per offset, one byte-permute selector per slot pair);
+//   * the tile's coordinates are wave-uniform (callers pass a readfirstlane'd wave, and the
+//     4 windows of a tile share wi >> lg for lg >= 2): position, division by 13 and row base
+//     are scalar work, the lane adds a constant of its own.
+constexpr int WF_BYTES = 2 * 64 * 16;            // wf[nt][lane]: one bf16x8 B fragment each
+constexpr int CONV_LDS_BYTES = WF_BYTES + NF * 4;  // + [32] fp32 biases
 struct ConvFrag {
   bf16x8 w[2];
   float bias[2];
-  int toff[8];
-  uint32_t lomask[8], zmask[8];
+  int lbase;        // byte offset in xs of the lane's pixel (window r >> 2, sub-pixel r & 3) within the tile
+  uint32_t tb[2];   // byte offsets of the 8 gathers, one per byte
+  uint32_t sel[4];  // v_perm selectors of the 4 slot pairs: hi, lo or zero per half
 };
-// A conv weight as the MFMA operand takes it: bf16 hi | bf16 lo << 16 (w = hi + lo), in one
-// 32-bit LDS word.  The thread that owns the parameter's update splits it once; conv_setup
-// of every wave then only selects a half (split per wave and lane, the 16 conversions and
-// subtractions of conv_setup sat on the conv phase's VALU-issue-bound path once per wave).
-__device__ __forceinline__ float conv_w_split(float w32) {
-  const uint32_t hi = f2bf(w32), lo = bf16_lo(w32, (uint16_t)hi);
-  return __uint_as_float(hi | (lo << 16));
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+// byte offset of tap t = (ty, tx) from a window pixel
+constexpr uint32_t tap_off4(int t) { return 4u * (uint32_t)(t + (IMG - 3) * (t / 3)); }
+constexpr uint32_t gather_word(int kg, int half) {
+  uint32_t w = 0;
+  for (int i = 0; i < 4; ++i) w |= tap_off4((4 * half + i - kg + 9) % 9) << (8 * i);
+  return w;
 }
-// cw: [288] split weights (conv_w_split), [32] fp32 biases
-__device__ __forceinline__ void conv_setup(ConvFrag& f, const float* cw, int lane) {
-  const int kg = lane >> 4;
-  // slot k = 8 kg + j: tap (8 kg + j) mod 9 = (j - kg) mod 9; the x-lo slots (part 1, k in
-  // [9, 18)), w-lo slots (part 2, [18, 27)) and zero slots (k >= 27) of group kg as bit masks
-  // over j -- shifts and selects, not the divisions by 9 and 3 (~10 VALU per slot, sunk by
-  // hipcc into the conv loop)
-  const unsigned xlo = (0x0003FE00u >> (8 * kg)) & 0xffu, wlo = (0x07FC0000u >> (8 * kg)) & 0xffu;
-  const unsigned zer = kg == 3 ? 0xF8u : 0u;
-  int tapj[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int t = j - kg;
-    tapj[j] = t < 0 ? t + 9 : t;
-    f.toff[j] = tapj[j] + (IMG - 3) * ((tapj[j] * 11) >> 5);  // (tap / 3) * IMG + tap % 3, tap < 9
-    f.lomask[j] = (xlo >> j) & 1u ? 0xffffu : 0u;
-    f.zmask[j] = (zer >> j) & 1u ? 0u : 0xffffu;
-  }
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    s16x8 t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t hl = __float_as_uint(cw[tapj[j] * NF + 16 * nt + (lane & 15)]);
-      t[j] = (short)(((wlo >> j) & 1u ? hl >> 16 : hl) & f.zmask[j]);
-    }
-    f.w[nt] = __builtin_bit_cast(bf16x8, t);
-    f.bias[nt] = cw[OFF_BC + 16 * nt + (lane & 15)];
-  }
+// v_perm_b32(hi pair, lo pair, sel): selector bytes 4-7 take the hi pair's bytes, 0-3 the lo
+// pair's, 0x0c gives 0x00.  K slot k takes x_hi (k < 9 and 18 <= k < 27), x_lo (9 <= k < 18)
+// or zero (k >= 27); element e of a pair fills the low (e = 0) or high half of the word.
+constexpr uint32_t half_sel(int k, int e) {
+  return k >= 27 ? 0x0c0cu : (k >= 9 && k < 18) ? (e ? 0x0302u : 0x0100u) : (e ? 0x0706u : 0x0504u);
 }
-// emit(image, pl, channel, pooled_bf16, code) for every pooled output of the slice
+constexpr uint32_t pair_sel(int kg, int p) {
+  return half_sel(8 * kg + 2 * p, 0) | (half_sel(8 * kg + 2 * p + 1, 1) << 16);
+}
+static_assert(tap_off4(8) < 256, "gather offsets fit a byte");
+// index (bf16 elements) in wf of K slot k of channel c: fragment nt = c >> 4, lane
+// (k >> 3) * 16 + (c & 15), element k & 7
+__device__ __forceinline__ int wf_slot(int k, int c) {
+  return (((c >> 4) * 64 + (c & 15)) << 3) + ((k >> 3) << 7) + (k & 7);
+}
+// The thread that owns the update of conv weight (tap t, channel c) splits it once
+// (w = hi + lo in bf16) and stores the halves where the MFMA operand takes them: hi at K
+// slots t and t + 9, lo at t + 18 (split per wave and lane, the conversions, selects and
+// packing sat on the conv phase's VALU-issue-bound path once per wave).
+// ws: the thread's slots (conv_w_slots), computed ahead of the loads the update waits for.
+__device__ __forceinline__ void conv_w_store(uint16_t* wf, const int* ws, float w32) {
+  const uint16_t hi = f2bf(w32), lo = bf16_lo(w32, hi);
+  wf[ws[0]] = hi;
+  wf[ws[1]] = hi;
+  wf[ws[2]] = lo;
+}
+// Thread i < 288 owns conv weight i = (tap i >> 5, channel i & 31): its three slots.  Threads
+// NCONV <= i < NCONV + 160 zero the 5 x 32 pad slots (k >= 27), ws[0] each.
+__device__ __forceinline__ void conv_w_slots(int* ws, int i) {
+  const int t = i >> 5, c = i & (NF - 1);
+  ws[0] = i < NCONV ? wf_slot(t, c) : wf_slot(27 + ((i - NCONV) >> 5), c);
+  ws[1] = wf_slot(t + 9, c);
+  ws[2] = wf_slot(t + 18, c);
+}
+// wf: the weight fragments (conv_w_store, pad slots zeroed), cb: [32] fp32 biases
+__device__ __forceinline__ void conv_setup(ConvFrag& f, const uint16_t* wf, const float* cb, int lane) {
+  const int kg = lane >> 4, r = lane & 15;
+  f.w[0] = ld_frag(wf + lane * 8);
+  f.w[1] = ld_frag(wf + (64 + lane) * 8);
+  f.bias[0] = cb[r];
+  f.bias[1] = cb[16 + r];
+  f.lbase = 4 * (((r >> 2) * XR + ((r >> 1) & 1)) * IMG + (r & 1));
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    f.tb[i] = kg == 0 ? gather_word(0, i) : kg == 1 ? gather_word(1, i) : kg == 2 ? gather_word(2, i) : gather_word(3, i);
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    f.sel[p] = kg == 0 ? pair_sel(0, p) : kg == 1 ? pair_sel(1, p) : kg == 2 ? pair_sel(2, p) : pair_sel(3, p);
+}
+// emit(image base, image offset, pl, channel, pooled_bf16, code) for every pooled output of the
+// slice; the image is base + offset: base and pl are wave-uniform, offset = lane >> 4 and the
+// channel depend on the lane only
 // One row tile: the A fragment (8 LDS gathers, hi/lo split), then per channel half nt one
 // MFMA and one bias / ReLU / pool / argmax epilogue.  HALF: only the channel half h (a
 // wave-uniform runtime value) -- the two halves of a tile share nothing but the A fragment,
 // so a tile split over two waves gives the same bits as one built by a single wave.
+// rt (wave-uniform): windows wi = 4 rt .. 4 rt + 3 = position pl = rt >> (lg - 2), images
+// b0 .. b0 + 3 with b0 = 4 rt mod 2^lg (lg >= 2: a tile never straddles two positions)
 template <bool HALF, class Emit>
 __device__ __forceinline__ void conv_tile(const ConvFrag& f, const float* xs, int p0, int r0, int lg, int rt, int h,
                                           int lane, Emit&& emit) {
-  s16x8 at;
+  const int pl = rt >> (lg - 2), b0 = (4 * rt) & ((1 << lg) - 1);
+  u32x4v at;
   {
-    const int r = lane & 15, wi = 4 * rt + (r >> 2), sub = r & 3;
-    const int pl = wi >> lg, b = wi & ((1 << lg) - 1), pos = p0 + pl, py = pos / PO, px = pos - py * PO;
-    const float* base = xs + (b * XR + 2 * py - r0 + (sub >> 1)) * IMG + 2 * px + (sub & 1);
+    const int pos = p0 + pl, py = pos / PO, px = pos - py * PO;
+    const char* base = reinterpret_cast<const char*>(xs + ((b0 * XR + 2 * py - r0) * IMG + 2 * px)) + f.lbase;
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = base[f.toff[j]];
+    for (int j = 0; j < 8; ++j)
+      v[j] = *reinterpret_cast<const float*>(base + ((f.tb[j >> 2] >> (8 * (j & 3))) & 0xffu));
+    // x = hi + lo in bf16, a pair at a time: elementwise the values of f2bf / bf16_lo
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t hi = f2bf(v[j]), lo = bf16_lo(v[j], (uint16_t)hi);
-      at[j] = (short)((hi ^ ((hi ^ lo) & f.lomask[j])) & f.zmask[j]);
+    for (int p = 0; p < 4; ++p) {
+      const f32x2v v2 = {v[2 * p], v[2 * p + 1]};
+      const uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, bf16x2v));
+      const f32x2v hf = {__uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
+      const uint32_t lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2 - hf, bf16x2v));
+      at[p] = __builtin_amdgcn_perm(hi, lo, f.sel[p]);
     }
   }
   const bf16x8 a = __builtin_bit_cast(bf16x8, at);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  const int wo = 4 * rt + (lane >> 4), plo = wo >> lg, bo = wo & ((1 << lg) - 1);
+  const int plo = pl, bo = lane >> 4;
   auto epilogue = [&](const f32x4& cc, float bias, int ch0) __attribute__((always_inline)) {
     float best = fmaxf(cc[0] + bias, 0.f);
     int arg = 0;
@@ -223,7 +264,7 @@ __device__ __forceinline__ void conv_tile(const ConvFrag& f, const float* xs, in
       arg = v > best ? j : arg;
       best = fmaxf(best, v);
     }
-    emit(bo, plo, ch0 + (lane & 15), f2bf(best), (uint8_t)(arg | (best > 0.f ? 4 : 0)));
+    emit(b0, bo, plo, ch0 + (lane & 15), f2bf(best), (uint8_t)(arg | (best > 0.f ? 4 : 0)));
   };
   if constexpr (HALF) {
     const bf16x8 w = h ? f.w[1] : f.w[0];
@@ -238,7 +279,7 @@ __device__ __forceinline__ void conv_tile(const ConvFrag& f, const float* xs, in
 // The slice's row tiles over the block's NW waves.  SPLIT = false: round-robin, whole tiles
 // (with 12 tiles on 8 waves four waves build two, four build one).  SPLIT = true: whole tiles
 // for the full rounds, the leftover tiles split by channel half over twice as many waves
-// (12 tiles on 8 waves: one tile plus one half tile each).
+// (12 tiles on 8 waves: one tile plus one half tile each).  wave: wave-uniform (readfirstlane).
 template <int NW, bool SPLIT, class Emit>
 __device__ __forceinline__ void conv_pool(const ConvFrag& f, const float* xs, int p0, int np, int r0, int lg,
                                           int wave, int lane, Emit&& emit) {

@@ -149,7 +149,8 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
 // from BAL -- its 12 tiles are 3 per SIMD whatever the wave count, and the SIMD's VALU issue
 // is the limit (the waves that share a SIMD with an older one arrive last) -- but with 12
 // waves the prologue is shorter (one W1 unit per thread) and eight waves, not four, move the
-// stores while four run dense-1; BAL = 2 (a duplicated A-fragment build) loses.
+// stores while four run dense-1; BAL = 2 (a duplicated A-fragment build) loses.  Re-checked in
+// round 10, after the conv phase lost its lane-constant setup: BAL = 0 is still slower than 1.
 #ifndef DAMD_FWD_BAL
 #define DAMD_FWD_BAL 1
 #endif
@@ -235,7 +236,9 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const int B = SPEC ? CH : bpp & 0xffff, PP = SPEC ? C::PP : bpp >> 16, lg = SPEC ? C::LG : lge & 0xff;
   const int eager = SPEC ? 1 : lge >> 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  // (wave through readfirstlane: the compiler then knows it is uniform, so a tile's coordinates
+  // are scalar work and the role branches -- wave < ntiles -- scalar branches)
+  const int s = blockIdx.x, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const bool sh = C::SH && xa.world > 1;  // sharded multi-rank step: gradients from the exchange staging
   constexpr int hprobe = DAMD_PROBE_HACC;  // 0 in every product build (see the top of the file)
   // (constant configuration: the grid is NS x B / IB blocks, every image group is full)
@@ -253,7 +256,9 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   float* xs = reinterpret_cast<float*>(smem);                              // [IB][XR][28]; later [IB][64] partials
   uint16_t* as = reinterpret_cast<uint16_t*>(smem + IB * XR * IMG * 4);    // [IB][KP] pooled tile
   uint16_t* w1t = as + IB * KP;                                            // [HID][KP] W1 slice^T
-  float* cw = reinterpret_cast<float*>(w1t + HID * KP);                    // [320] conv params
+  uint16_t* wf = w1t + HID * KP;                                           // [2][64][8] conv weight fragments
+  float* cb = reinterpret_cast<float*>(wf + WF_BYTES / 2);                 // [32] conv biases
+  static_assert(NT >= NCONV + 5 * NF, "threads past the conv parameters zero the pad slots");
   const int n4 = K * HID / 4;  // <= 2048
   const int r0 = 2 * (p0 / PO);
   const int nrows = 2 * ((p1 - 1) / PO) + 4 - r0;
@@ -294,6 +299,10 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const bool small_on = lin >= nblk - 2 && si >= 0 && si < NSMALL;
   const int sic = OFF_B1 + max(0, min(si, NSMALL - 1));
   const float sp = P[sic], sg0 = sh ? 0.f : G[sic], sv = V[sic];
+  // where this thread's conv weight goes in the LDS fragment table: address math while the
+  // loads above are in flight, not behind the wait for them
+  int wfs[3];
+  conv_w_slots(wfs, tid);
   __builtin_amdgcn_sched_barrier(0);
 
   const Ctrl c = *ctrl;
@@ -430,11 +439,14 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   float cwn = 0.f, cvn = 0.f;
   if (tid < NCONV) {
     sgd_or_keep(pend, cp, from_fix(cq, CINV), cv, c, cwn, cvn);
-    cw[tid] = tid < OFF_BC ? conv_w_split(cwn) : cwn;  // weights: split once here, not per wave and lane
+    // weights: split once here and stored in MFMA operand order, not per wave and lane
+    if (tid < OFF_BC) conv_w_store(wf, wfs, cwn);
+    else cb[tid - OFF_BC] = cwn;
     // the conv epilogue's ReLU (fmaxf) and the head's would turn a NaN parameter into 0:
     // a non-finite conv / b1 / W2 / b2 value raises ctrl.bad (loss NaN) here instead
     if (!__builtin_isfinite(cwn)) __hip_atomic_fetch_or(&ctrl->bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if (tid >= NCONV && tid < NCONV + 5 * NF) wf[wfs[0]] = 0;
   if (small_on) {
     float wn, vn;
     sgd_or_keep(pend, sp, sg, sv, c, wn, vn);
@@ -454,14 +466,15 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   stamp(sts, st, 2);
 
   ConvFrag cf;
-  conv_setup(cf, cw, lane);
+  conv_setup(cf, wf, cb, lane);
   stamp(sts, st, 5);
-  uint8_t* csl = reinterpret_cast<uint8_t*>(cw + NCONV);  // [IB][KC] argmax codes
-  conv_pool<NW, C::BAL == 2>(cf, xs, p0, npl, r0, lg, wave, lane, [&](int bo, int plo, int ch, uint16_t hb, uint8_t cd) {
+  uint8_t* csl = reinterpret_cast<uint8_t*>(cb + NF);  // [IB][KC] argmax codes
+  // (image bu + bl: bu and plo are wave-uniform, so the tile's store base is scalar work)
+  conv_pool<NW, C::BAL == 2>(cf, xs, p0, npl, r0, lg, wave, lane, [&](int bu, int bl, int plo, int ch, uint16_t hb, uint8_t cd) {
     // (constant configuration: positions >= NPOS of the last slice were computed from rows
     // nobody staged; their pooled value is 0, their code is never stored)
-    as[bo * KP + plo * 32 + ch] = SPEC && plo >= np ? (uint16_t)0 : hb;
-    csl[bo * KC + plo * 32 + ch] = cd;
+    as[(bu * KP + plo * 32) + (bl * KP + ch)] = SPEC && plo >= np ? (uint16_t)0 : hb;
+    csl[(bu * KC + plo * 32) + (bl * KC + ch)] = cd;
   });
   stamp(sts, st, 6);
   lds_barrier();
@@ -1583,7 +1596,7 @@ size_t convnet2_fwd_lds(int PP, int lg) {
   using namespace convnet;
   const int KP = kpitch(PP), IB = 1 << lg;
   const size_t xsb = (size_t)IB * XR * IMG * 4, partb = (size_t)IB * HID * 4;
-  return (xsb > partb ? xsb : partb) + (size_t)(IB + HID) * KP * 2 + NCONV * 4 + (size_t)IB * PP * 32 + 256 * 4;
+  return (xsb > partb ? xsb : partb) + (size_t)(IB + HID) * KP * 2 + CONV_LDS_BYTES + (size_t)IB * PP * 32 + 256 * 4;
 }
 // flagship: the layout of bwd_flag (CfgFlagBwd::AUX: dps in a region of its own behind the head
 // scratch instead of aliasing it)

@@ -20,7 +20,50 @@ __global__ __launch_bounds__(64) void spin_stamp_k(long long ticks, unsigned lon
   }
 }
 
+// Test-only pair (tests/test_convnet_fwd_lds_poison_gpu.py): LDS is not cleared between
+// workgroups, so a kernel that reads a word nobody staged sees what an earlier workgroup on
+// the CU left there.  lds_poison_k fills each workgroup's whole LDS (one workgroup per CU at
+// this size) with 0x7FC07FC0 -- a quiet NaN as fp32 and as two bf16 --; lds_count_k counts
+// that pattern in LDS it never wrote (0: this device does not retain LDS contents).
+constexpr int LDS_ALL = 160 * 1024, LDS_WORDS = LDS_ALL / 4;
+constexpr unsigned LDS_POISON = 0x7FC07FC0u;
+
+__global__ __launch_bounds__(1024) void lds_poison_k() {
+  extern __shared__ __attribute__((aligned(16))) unsigned lds_words[];
+  for (int i = threadIdx.x; i < LDS_WORDS; i += 1024) lds_words[i] = LDS_POISON;
+  // (nothing reads the words in this kernel: the asm keeps the stores, and waits for them)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+__global__ __launch_bounds__(1024) void lds_count_k(unsigned long long* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned lds_words[];
+  unsigned n = 0;
+  for (int i = threadIdx.x; i < LDS_WORDS; i += 1024) n += lds_words[i] == LDS_POISON ? 1u : 0u;
+  if (n) __hip_atomic_fetch_add(out, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+hipError_t lds_all(const void* k) {
+  return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
+}
+
 }  // namespace
+
+hipError_t lds_poison(int blocks, hipStream_t s) {
+  if (blocks < 1 || blocks > 65536) return hipErrorInvalidValue;
+  const hipError_t e = lds_all((const void*)lds_poison_k);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lds_poison_k, dim3(blocks), dim3(1024), LDS_ALL, s);
+  return hipGetLastError();
+}
+
+// adds to *out the number of poison words the blocks found in LDS they did not write
+hipError_t lds_count(int blocks, unsigned long long* out, hipStream_t s) {
+  if (blocks < 1 || blocks > 65536 || out == nullptr) return hipErrorInvalidValue;
+  const hipError_t e = lds_all((const void*)lds_count_k);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lds_count_k, dim3(blocks), dim3(1024), LDS_ALL, s, out);
+  return hipGetLastError();
+}
 
 hipError_t spin_stamp(long long ticks, int blocks, unsigned long long* out, int slot, hipStream_t s) {
   if (blocks < 1 || ticks < 0) return hipErrorInvalidValue;

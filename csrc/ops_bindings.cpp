@@ -32,12 +32,22 @@ damd::PoolGeo geo_(const std::vector<int>& g) {
 
 namespace damd {
 hipError_t spin_stamp(long long ticks, int blocks, unsigned long long* out, int slot, hipStream_t s);
+hipError_t lds_poison(int blocks, hipStream_t s);
+hipError_t lds_count(int blocks, unsigned long long* out, hipStream_t s);
 }
 
 void register_kernel_ops(py::module_& m) {
   // diagnostics (csrc/kernels/diag.hip): blocks holding their CU for `ticks` x 10 ns
   m.def("spin_stamp", [](long long ticks, int blocks, uintptr_t out, int slot, uintptr_t s) {
     check(damd::spin_stamp(ticks, blocks, P_<unsigned long long>(out), slot, P_<ihipStream_t>(s)), "spin_stamp");
+  });
+  // tests only: every block fills its whole LDS with a NaN pattern / counts that pattern in
+  // LDS it did not write (added to the uint64 at `out`)
+  m.def("lds_poison", [](int blocks, uintptr_t s) {
+    check(damd::lds_poison(blocks, P_<ihipStream_t>(s)), "lds_poison");
+  });
+  m.def("lds_count", [](int blocks, uintptr_t out, uintptr_t s) {
+    check(damd::lds_count(blocks, P_<unsigned long long>(out), P_<ihipStream_t>(s)), "lds_count");
   });
   m.def(
       "gemm",
