@@ -103,6 +103,22 @@ hipError_t pool_bn_bwd_apply(const uint16_t* dpool, const uint8_t* arg, const Po
 hipError_t gap_fwd(const uint16_t* x, int N, int HW, int C, void* y, int y_f32, hipStream_t s);
 hipError_t gap_bwd(const void* dy, int dy_f32, int N, int HW, int C, uint16_t* dx, hipStream_t s);
 
+// Depthwise convolution (csrc/kernels/dwconv.hip), depth_multiplier 1 ------------------------
+// PoolGeo with ph x pw the kernel; w: the taps [ph * pw][C] bf16 (16-byte aligned).
+// y = bf16(act(sum of the in-bounds taps (fp32, (i, j) order) + bias)); bias fp32 [C] or null,
+// relu 0 / 1
+hipError_t dwconv_fwd(const uint16_t* x, const uint16_t* w, const float* bias, int relu, const PoolGeo& g,
+                      uint16_t* y, hipStream_t s);
+// dx = the gather of dy over the taps that reach each input pixel; EVERY dx element is written
+hipError_t dwconv_dgrad(const uint16_t* dy, const uint16_t* w, const PoolGeo& g, uint16_t* dx, hipStream_t s);
+// dw [ph * pw][C] fp32 += sum over the output pixels of x * dy, in a fixed order (no float
+// atomics): dwconv_wgrad_blocks(g) pixel slabs write one partial row each into ws
+// ([blocks][ph * pw * C] fp32), a second pass adds the rows in order.  Square kernels up to 7 x 7.
+int dwconv_wgrad_blocks(const PoolGeo& g);
+hipError_t dwconv_wgrad(const uint16_t* x, const uint16_t* dy, const PoolGeo& g, float* dw, float* ws, hipStream_t s);
+// blocks a forward / backprop-input launch runs at most (grid-stride beyond)
+int dwconv_grid_cap();
+
 // Elementwise -----------------------------------------------------------------------------
 // dz = dy * [y > 0]  (bf16)
 hipError_t relu_bwd(const uint16_t* dy, const uint16_t* y, uint16_t* dz, long n, hipStream_t s);

@@ -298,6 +298,22 @@ void register_kernel_ops(py::module_& m) {
   m.def("avgpool_bwd", [](U dy, std::vector<int> g, U dx, U s) {
     check(damd::avgpool_bwd(P_<const u16>(dy), geo_(g), P_<u16>(dx), P_<ihipStream_t>(s)), "avgpool_bwd");
   });
+  m.def("dwconv_fwd", [](U x, U w, U bias, int relu, std::vector<int> g, U y, U s) {
+    check(damd::dwconv_fwd(P_<const u16>(x), P_<const u16>(w), P_<const float>(bias), relu, geo_(g), P_<u16>(y),
+                           P_<ihipStream_t>(s)),
+          "dwconv_fwd");
+  });
+  m.def("dwconv_dgrad", [](U dy, U w, std::vector<int> g, U dx, U s) {
+    check(damd::dwconv_dgrad(P_<const u16>(dy), P_<const u16>(w), geo_(g), P_<u16>(dx), P_<ihipStream_t>(s)),
+          "dwconv_dgrad");
+  });
+  m.def("dwconv_wgrad", [](U x, U dy, std::vector<int> g, U dw, U ws, U s) {
+    check(damd::dwconv_wgrad(P_<const u16>(x), P_<const u16>(dy), geo_(g), P_<float>(dw), P_<float>(ws),
+                             P_<ihipStream_t>(s)),
+          "dwconv_wgrad");
+  });
+  m.def("dwconv_wgrad_blocks", [](std::vector<int> g) { return damd::dwconv_wgrad_blocks(geo_(g)); });
+  m.def("dwconv_grid_cap", &damd::dwconv_grid_cap);
   m.def("bn_infer_st", [](U rmean, U rvar, U gamma, U beta, float eps, int C, U st, U s) {
     check(damd::bn_infer_st(P_<const float>(rmean), P_<const float>(rvar), P_<const float>(gamma),
                             P_<const float>(beta), eps, C, P_<float>(st), P_<ihipStream_t>(s)),

@@ -128,6 +128,14 @@ class PlanExec:
                     ws = max(ws, H.colsum_workspace_elems(int(np.prod(nd.out.shape[:-1])), cout))
                 if _act_name(l) != "linear":
                     nd.attrs["dz"] = torch.zeros(nd.out.shape, dtype=torch.bfloat16, device=dev)
+            elif k == "DepthwiseConv2D":
+                l = nd.layer
+                nd.attrs["geo"] = g = H.pool_geo(nd.inputs[0].root().shape, l.kernel_size, l.strides, l.padding)
+                ws = max(ws, H.dwconv_wgrad_workspace_elems(g))
+                if l.use_bias:
+                    ws = max(ws, H.colsum_workspace_elems(int(np.prod(nd.out.shape[:-1])), nd.out.shape[-1]))
+                if _act_name(l) != "linear":
+                    nd.attrs["dz"] = torch.zeros(nd.out.shape, dtype=torch.bfloat16, device=dev)
             elif k == "BatchNormalization":
                 C = nd.out.shape[-1]
                 M = int(np.prod(nd.out.shape[:-1]))
@@ -283,6 +291,14 @@ class PlanExec:
             H.conv_fwd(bn.inputs[0].root().buf if bn is not None else x, wb, nd.out.root().buf, l.strides, l.padding,
                        bias=bias, relu=relu, stats=nd.attrs.get("stats_buf"), workspace=self.gemm_ws,
                        bnin=(bn.attrs["fin"], x) if bn is not None else None)
+        self._act_epilogue(nd)
+
+    def _fwd_DepthwiseConv2D(self, nd):
+        # (also the depthwise half of a SeparableConv2D: no bias, linear)
+        l = nd.layer
+        bias = self.params.view(l.bias) if l.use_bias else None
+        H.dwconv_fwd(nd.inputs[0].root().buf, self.params.bview(l.depthwise_kernel), bias,
+                     _act_name(l) == "relu", nd.attrs["geo"], nd.out.root().buf)
         self._act_epilogue(nd)
 
     def pad_job(self, nd):

@@ -457,6 +457,21 @@ class NativeGraphEngine(Engine):
         else:
             H.conv_wgrad(xt.buf, dy, self.params.gview(l.kernel), l.strides, l.padding, workspace=ws)
 
+    def _bwd_DepthwiseConv2D(self, nd):
+        l = nd.layer
+        xt = nd.inputs[0].root()
+        y = nd.out.root()
+        dy, g = y.grad, nd.attrs["geo"]
+        if "dz" in nd.attrs:
+            self._act_bwd(nd, dy, y.buf, nd.attrs["dz"])
+            dy = nd.attrs["dz"]
+        if l.use_bias:
+            H.colsum(dy, self.params.gview(l.bias), workspace=self.gemm_ws)
+        H.dwconv_wgrad(xt.buf, dy, g, self.params.gview(l.depthwise_kernel), workspace=self.gemm_ws)
+        with self._grad_into(xt) as dx:  # (a second writer: scratch + add_bf16)
+            if dx is not None:
+                H.dwconv_dgrad(dy, self.params.bview(l.depthwise_kernel), g, dx)
+
     def _bn_backward(self, bn, dy, ymask, relu, dz_out=None, mask_from_x=False):
         """BatchNorm backward of node ``bn`` for upstream gradient dy (masked by
         [ymask > 0] when relu); dgamma/dbeta into the gradient sinks, dx into the input's

@@ -7,6 +7,10 @@ Fusion rules (decided on the layer graph, not traced):
   BatchNormalization -> ReLU                    : ReLU in the BN apply
   BatchNormalization -> Add(other) [-> ReLU]    : residual add (+ the other branch's own
                                                   BN when it is BN-terminated) in one pass
+
+With DAMD_NATIVE_DEPTHWISE=1 (off by default) DepthwiseConv2D plans as a node of its own and
+SeparableConv2D as two: a DepthwiseConv2D node (no bias, linear) and a 1 x 1 Conv2D node over
+a planned intermediate tensor, so the rules above apply to the pointwise half unchanged.
 """
 from __future__ import annotations
 
@@ -246,6 +250,59 @@ def _opt_kernel_slots(opt):
 SUPPORTED = ("Conv2D", "BatchNormalization", "Activation", "ReLU", "Add", "MaxPooling2D",
              "AveragePooling2D", "GlobalAveragePooling2D", "Flatten", "Dense", "Dropout")
 ACTIVATIONS = ("linear", "relu", "sigmoid", "tanh")
+# with DAMD_NATIVE_DEPTHWISE=1 (off by default): csrc/kernels/dwconv.hip, depth_multiplier 1
+DEPTHWISE = ("DepthwiseConv2D", "SeparableConv2D")
+
+
+def native_depthwise() -> bool:
+    return env.get_bool("DAMD_NATIVE_DEPTHWISE", False)
+
+
+def _depthwise_ok(k, l):
+    """(ok, reason) of a DepthwiseConv2D / SeparableConv2D layer for the dwconv kernels."""
+    if l.depth_multiplier != 1:
+        return False, f"depthwise depth_multiplier {l.depth_multiplier}"
+    ks, st = tuple(l.kernel_size), tuple(l.strides)
+    if (tuple(l.dilation_rate) != (1, 1) or ks[0] != ks[1] or ks[0] > H.DWCONV_MAX_K or st[0] != st[1]
+            or st[0] not in (1, 2)):
+        return False, "depthwise geometry"
+    if l.depthwise_kernel.shape[2] % 8:
+        return False, "depthwise input channels must be a multiple of 8"
+    if k == "SeparableConv2D" and l.filters % 8:
+        return False, "separable filters must be a multiple of 8"
+    an = _act_name(l)
+    if an not in ACTIVATIONS:
+        return False, f"activation {an}"
+    return True, ""
+
+
+class SeparableDepthwise:
+    """The depthwise half of a SeparableConv2D as a DepthwiseConv2D node's layer (read-only):
+    the layer's kernel size, strides and padding; no bias, linear."""
+    use_bias, bias, activation, depth_multiplier, dilation_rate = False, None, None, 1, (1, 1)
+
+    def __init__(self, layer):
+        self.layer, self.name = layer, layer.name + "/depthwise"
+
+    depthwise_kernel = property(lambda self: self.layer.depthwise_kernel)
+    kernel_size = property(lambda self: tuple(self.layer.kernel_size))
+    strides = property(lambda self: tuple(self.layer.strides))
+    padding = property(lambda self: self.layer.padding)
+
+
+class SeparablePointwise:
+    """The pointwise half of a SeparableConv2D as a Conv2D node's layer (read-only): a 1 x 1
+    'valid' convolution by ``pointwise_kernel`` with the layer's bias and activation."""
+    kernel_size, strides, padding, dilation_rate = (1, 1), (1, 1), "valid", (1, 1)
+
+    def __init__(self, layer):
+        self.layer, self.name = layer, layer.name + "/pointwise"
+
+    kernel = property(lambda self: self.layer.pointwise_kernel)
+    filters = property(lambda self: self.layer.filters)
+    use_bias = property(lambda self: self.layer.use_bias)
+    bias = property(lambda self: self.layer.bias)
+    activation = property(lambda self: self.layer.activation)
 
 
 def layers_eligible(model):
@@ -273,8 +330,12 @@ def layers_eligible(model):
             continue  # one augment launch behind gather_batch
         if k in H.AUG_LAYERS:
             return False, f"layer {k} is native only ahead of the first weight layer"
-        if k not in SUPPORTED:
+        if k not in SUPPORTED and not (k in DEPTHWISE and native_depthwise()):
             return False, f"layer {k}"
+        if k in DEPTHWISE:
+            ok, why = _depthwise_ok(k, l)
+            if not ok:
+                return False, why
         an = _act_name(l)
         if (k in ("Conv2D", "Dense", "Activation") and an not in ACTIVATIONS
                 and l is not head_dense):
@@ -338,6 +399,16 @@ class Plan:
                 continue
             kind = type(layer).__name__
             xs = [tensors[i] for i in ins]
+            if kind == "SeparableConv2D":
+                # two nodes over a planned bf16 intermediate: the depthwise half (no bias,
+                # linear), then a 1 x 1 Conv2D by the pointwise kernel with the layer's bias and
+                # activation -- every Conv2D rule (BN-statistics epilogue, ...) applies to it
+                dw = SeparableDepthwise(layer)
+                mid = Node("DepthwiseConv2D", dw, xs, T(self._out_shape("DepthwiseConv2D", dw, xs)))
+                for x in xs:
+                    x.consumers.append(mid)
+                nodes.append(mid)
+                kind, layer, xs = "Conv2D", SeparablePointwise(layer), [mid.out]
             shp = self._out_shape(kind, layer, xs)
             out = T(shp)
             nd = Node(kind, layer, xs, out)
@@ -381,6 +452,10 @@ class Plan:
             ho, _ = H.conv_out(x[1], l.kernel_size[0], l.strides[0], l.padding)
             wo, _ = H.conv_out(x[2], l.kernel_size[1], l.strides[1], l.padding)
             return (B, ho, wo, l.filters)
+        if kind == "DepthwiseConv2D":
+            ho, _ = H.conv_out(x[1], l.kernel_size[0], l.strides[0], l.padding)
+            wo, _ = H.conv_out(x[2], l.kernel_size[1], l.strides[1], l.padding)
+            return (B, ho, wo, x[3])
         if kind in ("MaxPooling2D", "AveragePooling2D"):
             g = H.pool_geo(x, l.pool_size, l.strides, l.padding)
             return (B, g[10], g[11], x[3])
@@ -524,6 +599,8 @@ def plan_buckets(plan, variables, sizes, offsets, total_elems: int, bucket_mb: f
         if nd.kind in ("Conv2D", "Dense"):
             vs = [l.kernel] + ([l.bias] if l.use_bias else [])
             writers[id(nd)] = vs
+        elif nd.kind == "DepthwiseConv2D":
+            writers[id(nd)] = [l.depthwise_kernel] + ([l.bias] if l.use_bias else [])
         elif nd.kind == "BatchNormalization" and not nd.attrs.get("stats_only"):
             writers[id(nd)] = [w for w in (l.gamma, l.beta) if w is not None]
         elif nd.kind == "Add" and nd.attrs.get("fused"):

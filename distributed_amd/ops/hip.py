@@ -1144,6 +1144,69 @@ def avgpool_bwd(dy, dx, pool, strides, padding):
     _C().avgpool_bwd(_ptr(dy), g, _ptr(dx), stream_handle())
 
 
+# --- depthwise convolution (csrc/kernels/dwconv.hip), depth_multiplier 1 -----------------------
+# geo: the pool_geo(x.shape, kernel_size, strides, padding) list; w: the bf16 taps of the
+# depthwise kernel, [kh, kw, C, 1] or any view of kh * kw * C contiguous elements.
+DWCONV_MAX_K = 7
+
+
+def _dw_geo(geo, who):
+    n, h, w, c, kh, kw, sh, sw, pt, pl, ho, wo = geo
+    if c % 8:
+        raise ValueError(f"{who}: channels must be a multiple of 8")
+    return (n, h, w, c), (n, ho, wo, c), kh * kw * c
+
+
+def dwconv_fwd(x, w, bias, relu, geo, y):
+    """y [N,Ho,Wo,C] = bf16(act(depthwise conv of x [N,H,W,C] with taps w + bias)); bias fp32
+    [C] or None, act the identity or ReLU."""
+    xs, ys, nw = _dw_geo(geo, "dwconv_fwd")
+    _chk(x, torch.bfloat16, "x")
+    _chk(w, torch.bfloat16, "w")
+    _chk(y, torch.bfloat16, "y")
+    if bias is not None:
+        _chk(bias, torch.float32, "bias")
+        if bias.numel() != xs[3]:
+            raise ValueError("dwconv_fwd: bias must hold C values")
+    if tuple(x.shape) != xs or tuple(y.shape) != ys or w.numel() != nw:
+        raise ValueError(f"dwconv_fwd: x {tuple(x.shape)}, w {tuple(w.shape)}, y {tuple(y.shape)} against geometry "
+                         f"{geo}")
+    _C().dwconv_fwd(_ptr(x), _ptr(w), _ptr(bias), int(bool(relu)), list(geo), _ptr(y), stream_handle())
+
+
+def dwconv_dgrad(dy, w, geo, dx):
+    """dx [N,H,W,C] = the backprop-input of dwconv_fwd; every element is written."""
+    xs, ys, nw = _dw_geo(geo, "dwconv_dgrad")
+    _chk(dy, torch.bfloat16, "dy")
+    _chk(w, torch.bfloat16, "w")
+    _chk(dx, torch.bfloat16, "dx")
+    if tuple(dx.shape) != xs or tuple(dy.shape) != ys or w.numel() != nw:
+        raise ValueError(f"dwconv_dgrad: dy {tuple(dy.shape)}, w {tuple(w.shape)}, dx {tuple(dx.shape)} against "
+                         f"geometry {geo}")
+    _C().dwconv_dgrad(_ptr(dy), _ptr(w), list(geo), _ptr(dx), stream_handle())
+
+
+def dwconv_wgrad_workspace_elems(geo) -> int:
+    """fp32 workspace floats of dwconv_wgrad: one partial row [kh * kw * C] per pixel slab."""
+    return _C().dwconv_wgrad_blocks(list(geo)) * geo[4] * geo[5] * geo[3]
+
+
+def dwconv_wgrad(x, dy, geo, dw, workspace=None):
+    """dw (fp32, kh * kw * C elements) += sum over the output pixels of x * dy, in a fixed
+    order (no float atomics): repeated launches give the same bits."""
+    xs, ys, nw = _dw_geo(geo, "dwconv_wgrad")
+    _chk(x, torch.bfloat16, "x")
+    _chk(dy, torch.bfloat16, "dy")
+    _chk(dw, torch.float32, "dw")
+    if geo[4] != geo[5] or geo[4] > DWCONV_MAX_K:
+        raise ValueError(f"dwconv_wgrad: square kernels up to {DWCONV_MAX_K} x {DWCONV_MAX_K}")
+    if tuple(x.shape) != xs or tuple(dy.shape) != ys or dw.numel() != nw:
+        raise ValueError(f"dwconv_wgrad: x {tuple(x.shape)}, dy {tuple(dy.shape)}, dw {tuple(dw.shape)} against "
+                         f"geometry {geo}")
+    ws = _workspace(workspace, dwconv_wgrad_workspace_elems(geo), x.device)
+    _C().dwconv_wgrad(_ptr(x), _ptr(dy), list(geo), _ptr(dw), _ptr(ws), stream_handle())
+
+
 def add_bf16(a, b, out):
     _C().add_bf16(_ptr(a), _ptr(b), _ptr(out), a.numel(), stream_handle())
 

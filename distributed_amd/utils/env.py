@@ -36,6 +36,8 @@ def get_str(name: str, default: str) -> str:
 #   DAMD_BUCKET_MB         float               gradient all-reduce bucket size, native graph engine (8)
 #   DAMD_FORCE_ALLREDUCE   0/1                 keep the RCCL all-reduce in the step at world 1 (testing)
 #   DAMD_NATIVE_GRAPH      0/1                 allow the native graph engine (HIP plan + graph, default 1)
+#   DAMD_NATIVE_DEPTHWISE  0/1                 plan DepthwiseConv2D / SeparableConv2D natively (dwconv.hip;
+#                          default 0: they take the PyTorch-ops fallback)
 #   DAMD_GRAPH             0/1                 capture steps into hipGraphs (default 1)
 #   DAMD_GRAPH_STEPS       int                 steps per captured graph (default 20)
 #   DAMD_PP                1..4                pooled positions per fused slice (default 3)
