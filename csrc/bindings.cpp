@@ -47,6 +47,8 @@ class ConvNetTrainer : public StepExecutor {
     b_.ctrl = P_<Ctrl>(g("ctrl"));
     b_.pooled = P_<uint16_t>(g("pooled")); b_.code = P_<uint8_t>(g("code"));
     b_.W1alt = P_<float>(g("w1alt")); b_.V1alt = P_<float>(g("v1alt")); b_.w1bf = P_<uint16_t>(g("w1bf"));
+    // second parity buffer of the bf16 W1 copy (convnet.h; absent: one buffer, updated in place)
+    b_.w1bf_alt = bufs.contains("w1bf_alt") ? P_<uint16_t>(g("w1bf_alt")) : nullptr;
     b_.stamps = bufs.contains("stamps") ? P_<unsigned long long>(g("stamps")) : nullptr;
     b_.eager_w1 = bufs.contains("eager_w1") ? (int)g("eager_w1") : 0;
     b_.hacc = P_<long long>(g("hacc"));
@@ -186,6 +188,7 @@ class ConvNetTrainer : public StepExecutor {
   }
   void flush() {
     gather();
+    b_.par_hint = hint_ ? par_ : -1;  // (eager: which bf16 W1 buffer is live, convnet.h)
     HIP_CHECK(convnet2_launch_flush(b_, B_, stream_));
     par_ = 0;  // flush resets ctrl.wpar
   }
@@ -207,6 +210,7 @@ class ConvNetTrainer : public StepExecutor {
     return n;
   }
   int bwd_threads() const { return convnet2_bwd_threads(b_, B_, PP_); }
+  int bwd_blocks() const { return convnet2_bwd_blocks(b_, B_, PP_); }
   int bwd_compiled_threads() const {
     int n = 0;
     HIP_CHECK(convnet2_bwd_compiled_threads(b_, B_, PP_, &n));
@@ -293,6 +297,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("convnet2_lds_bytes", [](int PP) { return py::make_tuple(convnet2_fwd_lds(PP, 4), convnet2_bwd_lds(PP)); });
   // LDS bytes of the constant-configuration backward (bwd_flag) at its slice size
   m.def("convnet2_bwd_flag_lds_bytes", [](int PP) { return convnet2_bwd_lds(PP, true); });
+  // the flagship backward with a role per block: LDS bytes of role 0 (conv) / 1 (W1), blocks of
+  // its grid, and whether this build has the roles at all (DAMD_BWD_SPLIT)
+  m.def("convnet2_bwd_role_lds_bytes", &convnet2_bwd_role_lds, py::arg("positions_per_slice"), py::arg("role"));
+  m.def("convnet2_bwd_flag_blocks", &convnet2_bwd_flag_blocks);
+  m.def("convnet2_bwd_flag_split", &convnet2_bwd_flag_split);
   m.def("convnet_num_slices", &convnet_num_slices);
   m.def("convnet_hacc_elems", &convnet_hacc_elems);
   m.def("convnet_grad_count", &convnet_grad_count);
@@ -408,6 +417,7 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("fwd_compiled_threads", &ConvNetTrainer::fwd_compiled_threads)
       .def_property_readonly("bwd_threads", &ConvNetTrainer::bwd_threads)
       .def_property_readonly("bwd_compiled_threads", &ConvNetTrainer::bwd_compiled_threads)
+      .def_property_readonly("bwd_blocks", &ConvNetTrainer::bwd_blocks)
       .def_property_readonly("parity", &ConvNetTrainer::parity)
       .def_property_readonly("stream", [](ConvNetTrainer& t) { return reinterpret_cast<uintptr_t>(t.stream()); });
 

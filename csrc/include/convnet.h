@@ -39,6 +39,13 @@ struct ConvNetBuffers {
   int x_u8;
   float* P; float* G; float* V; Ctrl* ctrl;
   float* W1alt; float* V1alt; uint16_t* w1bf;  // W1 double buffer (fp32, velocity) + bf16 copy
+  // The bf16 copy is double-buffered by step parity (ctrl.wpar): w1bf is buffer 0, w1bf_alt
+  // buffer 1.  A step of parity p reads buffer p; the eager update in bwd writes buffer p ^ 1
+  // (the next step's), the deferred update in fwd buffer p; after flush buffer 0 is live.
+  // Whoever re-derives the copy from the masters on the host fills both.  Null: one buffer,
+  // updated in place -- safe only with one bwd block per slice, so the flagship step with a
+  // role per block (convnet2_specialised) is then refused and the generic kernels run
+  uint16_t* w1bf_alt;
   uint16_t* pooled /* [5408][BP] */; uint8_t* code /* [B][5408] */;
   unsigned long long* stamps;  // optional [3][256][16] phase stamps (diagnostics), may be null
   // fixed-point accumulators of the cross-block sums
@@ -91,6 +98,13 @@ int convnet_f1_lg(int B);
 size_t convnet2_fwd_lds(int PP, int lg);
 // flagship: the LDS layout of the constant-configuration backward (bwd_flag)
 size_t convnet2_bwd_lds(int PP, bool flagship = false);
+// the flagship backward with a role per block (DAMD_BWD_SPLIT, 1 = on): LDS bytes of one role
+// (0 conv, 1 W1; the launch asks for the larger), blocks of its grid (2 x slices, or slices)
+size_t convnet2_bwd_role_lds(int PP, int role);
+int convnet2_bwd_flag_blocks();
+int convnet2_bwd_flag_split();
+// blocks the bwd launch of a step with these buffers / sizes uses
+int convnet2_bwd_blocks(const ConvNetBuffers& b, int B, int PP);
 hipError_t convnet2_launch_step(const ConvNetBuffers& b, int B, int PP, hipStream_t st);
 // the two launches separately (phase timing)
 hipError_t convnet2_launch_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st);

@@ -30,8 +30,16 @@
 //       argmax codes fused into this slice's conv weight-gradient partial, added into
 //       hconv[par] as round(v * 2^40) with 64-bit atomics; the dead parity of hacc is
 //       zeroed for the next step.
+//       In the flagship configuration the two groups of work behind dh run on separate
+//       blocks (grid 2 NS, a role per block, see CfgFlagBwd::SPLIT): the conv role -- dP, the
+//       conv gradient, the hconv atomics -- is the kernel's critical chain; the W1 role --
+//       dW1, the eager update and its 2.1 MB of stores, the aux sums, the zeroing, the
+//       next-batch rows -- ends earlier, on CUs that used to idle.  Both run the head.
+//   The bf16 copy of W1 that fwd (dense-1) and bwd (dP) read has one buffer per step parity:
+//   a step of parity p reads buffer p, bwd's eager update writes buffer p ^ 1 (see below).
 //   No block waits on another: there is no ticket / last-arriver hand-off inside either
-//   launch (a returning atomic on a contended counter stalled its wave ~1.5-2 us).
+//   launch (a returning atomic on a contended counter stalled its wave ~1.5-2 us), and no
+//   block reads what another block of the same launch writes.
 //
 // Fixed point: h partials are fp32 MFMA sums of |v| < 2^31; x 2^32 keeps every bit a
 // float carries down to 2^-32 (the sum of 57 roundings is < 1.4e-8 absolute); conv
@@ -182,12 +190,44 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
 #ifndef DAMD_BWD_AUX
 #define DAMD_BWD_AUX 1
 #endif
+//   SPLIT   0 one block per slice runs the head and then both groups of work behind dh, one
+//           after the other; 1 a grid of 2 NS blocks, a role per block (block-uniform, scalar):
+//           blocks 0 .. NS - 1 the conv role of slice blockIdx.x, blocks NS .. 2 NS - 1 the W1
+//           role of slice blockIdx.x - NS.  Both run the head as before.
+//             conv role  stages the bf16 W1 slice, the argmax codes and the input rows; builds
+//                        only dhs (the A-operand layout of dh); dP MFMAs, the conv gradient, the
+//                        `red` hand-off (a region of its own: no barrier ahead of it) and the
+//                        hconv atomics.  The kernel's critical chain.
+//             W1 role    stages the pooled tile and the slice's fp32 masters / velocities; builds
+//                        only dht; dW1 MFMAs, the eager update and its stores; then everything
+//                        that sits off the chain: the aux sums and their b1 / W2 / b2 gradient and
+//                        metric-tail stores, the zeroing of the dead hacc parity, the next-batch
+//                        rows and their tag.
+//           Neither role executes the other's code or loads / stages its operands; block 0 alone
+//           advances the ctrl block.  The mapping of aux elements, zeroing ranges and next-batch
+//           units by slice is the unsplit kernel's, so every thread forms the same sums.
+//           The two blocks of a slice are not ordered: the conv role reads the bf16 W1 slice the
+//           W1 role rewrites, which is why the bf16 copy has one buffer per step parity (below).
+//           Measured (BENCH.md, round 11): 1 is the faster -- the conv role's chain ends 0.6 us
+//           earlier, the kernel 0.4 us.
+#ifndef DAMD_BWD_SPLIT
+#define DAMD_BWD_SPLIT 1
+#endif
+// The bf16 copy of W1 is double-buffered by step parity: in a step of parity p every reader
+// (fwd's dense-1 operand, bwd's dP operand) reads buffer p, and the eager update in bwd writes
+// buffer p ^ 1, which the next step (parity p ^ 1) reads; the deferred update in fwd writes
+// buffer p, which the same step's bwd reads.  flush leaves parity 0: it writes buffer 0
+// (deferred) or, eager, w1bf_live0 copies buffer 1 over buffer 0 first when the parity was 1.
+// No reader and writer of one launch share a buffer, so nothing depends on how blocks are
+// placed or ordered.  The kernels receive the pair as (live, other) when the host knows the
+// parity (par_hint >= 0) and as (buffer 0, buffer 1) when it does not; then they pick by the
+// ctrl block's parity and load the slice behind the ctrl block.
 struct CfgGeneric {
   static constexpr int PP = 0, LG = 0;
   static constexpr bool B64 = false, EAGER = false, SH = true;  // SH: may be sharded (xa.world)
   static constexpr int NT = 512, BAL = 0, STORES = 0;
   static constexpr bool D1REG = false;
-  static constexpr int AUX = 0;
+  static constexpr int AUX = 0, SPLIT = 0;
 };
 struct CfgFlagFwd {
   static constexpr int PP = 3, LG = 4;
@@ -199,8 +239,10 @@ struct CfgFlagFwd {
 struct CfgFlagBwd {
   static constexpr int PP = 2, LG = 0;
   static constexpr bool B64 = true, EAGER = true, SH = false;
-  static constexpr int NT = DAMD_BWD_NT, AUX = DAMD_BWD_AUX;
-  static_assert((NT == 512 || NT == 1024) && AUX >= 0 && AUX <= 1, "bwd wave mapping");
+  static constexpr int NT = DAMD_BWD_NT, AUX = DAMD_BWD_AUX, SPLIT = DAMD_BWD_SPLIT;
+  static_assert((NT == 512 || NT == 1024) && AUX >= 0 && AUX <= 1 && SPLIT >= 0 && SPLIT <= 1, "bwd wave mapping");
+  // blocks of the grid
+  static constexpr int NSC = (convnet::NPOS + PP - 1) / PP, GRID = SPLIT ? 2 * NSC : NSC;
 };
 // aux elements (b1/W2/b2 gradients + metric tail) per bwd block, and a power-of-two thread
 // count per element (<= 64) that fits them in 512 threads: chunk_aux | log2(threads) << 16
@@ -226,7 +268,8 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
                                          uint8_t* __restrict__ code, long long* __restrict__ hacc,
                                          long long* __restrict__ hconv, unsigned long long* st, const XArgs& xa,
                                          const long long* __restrict__ xtag, const int* __restrict__ labels,
-                                         void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+                                         void* __restrict__ xcur, int* __restrict__ ycur, int phint,
+                                         uint16_t* __restrict__ w1bf_alt) {
   constexpr bool SPEC = C::PP > 0;
   static_assert(!SPEC || (C::B64 && C::EAGER && !C::SH && C::LG == 4), "the one constant configuration");
   // threads / waves of the block, 16-byte units of the bf16 W1 slice per thread (eager)
@@ -277,7 +320,10 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   // barrier keeps them ahead of the ctrl load (left alone, hipcc issued the ctrl load first
   // and waited for it with the kernel arguments, then sank these below further waits) ----
   uint4 bq[NBQ];  // eager: the bf16 W1 slice (bwd already applied the update)
-  if (eager) {
+  // (the bf16 copy has one buffer per step parity: this step reads and -- deferred update --
+  // writes the live one.  Known parity: the host passed the live buffer as w1bf; else w1bf /
+  // w1bf_alt are buffers 0 / 1 and the load waits for the ctrl block's parity)
+  auto load_bq = [&](const uint16_t* __restrict__ src) __attribute__((always_inline)) {
     // (lanes past the slice load nothing: at PP = 2 the second unit is all out of range, and
     // its clamped duplicate loads were 8 KB per block of wasted load bandwidth.  Written as a
     // conditional load, not a select between pointers: hipcc turns the latter into a flat
@@ -285,9 +331,10 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
 #pragma unroll
     for (int u = 0; u < NBQ; ++u) {
       bq[u] = make_uint4(0u, 0u, 0u, 0u);
-      if (tid + u * NT < n4 / 2) bq[u] = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[tid + u * NT];
+      if (tid + u * NT < n4 / 2) bq[u] = reinterpret_cast<const uint4*>(src + p0 * 32 * HID)[tid + u * NT];
     }
-  }
+  };
+  if (eager && phint >= 0) load_bq(w1bf);
   // conv parameters: current buffer by parity; their gradient is the previous step's
   // (bwd added it into hconv[par ^ 1])
   const int tcl = min(tid, NCONV - 1);
@@ -319,6 +366,8 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const bool pend = c.pending != 0;
   const long row_base = (long)c.cursor * c.global_batch + c.row0 + img0;
   const bool mom = c.momentum != 0.f;
+  uint16_t* w1live = phint < 0 && par ? w1bf_alt : w1bf;  // the bf16 W1 buffer of this step's parity
+  if (eager && phint < 0) load_bq(w1live);
 
   // ---- then the ctrl-dependent loads: the batch rows unless prefetched (and, deferred
   // update, W1 by parity) ----
@@ -353,7 +402,7 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   const bool owner = blockIdx.y == 0;
   float4* Wn4 = reinterpret_cast<float4*>(Wnext + p0 * 32 * HID);
   float4* Vn4 = reinterpret_cast<float4*>(Vnext + p0 * 32 * HID);
-  uint2* Wb = reinterpret_cast<uint2*>(w1bf + p0 * 32 * HID);
+  uint2* Wb = reinterpret_cast<uint2*>(w1live + p0 * 32 * HID);
   if (!eager) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -623,9 +672,10 @@ __global__ __launch_bounds__(512) void fwd(const void* __restrict__ xnext, uint1
                                            uint8_t* __restrict__ code, long long* __restrict__ hacc,
                                            long long* __restrict__ hconv, unsigned long long* st, const XArgs xa,
                                            const long long* __restrict__ xtag, const int* __restrict__ labels,
-                                           void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+                                           void* __restrict__ xcur, int* __restrict__ ycur, int phint,
+                                           uint16_t* __restrict__ w1bf_alt) {
   fwd_body<U8, CfgGeneric>(xnext, w1bf, P, V, calt, hconv_r, G, bpp, lge, ctrl, X, W1alt, V1alt, pooled, code, hacc,
-                           hconv, st, xa, xtag, labels, xcur, ycur, phint);
+                           hconv, st, xa, xtag, labels, xcur, ycur, phint, w1bf_alt);
 }
 
 // The flagship configuration (CfgFlagFwd): no packed sizes, no exchange arguments, no W1
@@ -641,9 +691,10 @@ __global__ __launch_bounds__(CfgFlagFwd::NT) void fwd_flag(const void* __restric
                                                 uint16_t* __restrict__ pooled, uint8_t* __restrict__ code,
                                                 long long* __restrict__ hacc, long long* __restrict__ hconv,
                                                 unsigned long long* st, const int* __restrict__ labels,
-                                                void* __restrict__ xcur, int* __restrict__ ycur, int phint) {
+                                                void* __restrict__ xcur, int* __restrict__ ycur, int phint,
+                                                uint16_t* __restrict__ w1bf_alt) {
   fwd_body<U8, CfgFlagFwd>(xnext, w1bf, P, V, calt, hconv_r, G, 0, 0, ctrl, X, nullptr, nullptr, pooled, code, hacc,
-                           hconv, st, XArgs{}, xtag, labels, xcur, ycur, phint);
+                           hconv, st, XArgs{}, xtag, labels, xcur, ycur, phint, w1bf_alt);
 }
 
 // =================================================================================
@@ -777,8 +828,15 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   Stamps sts;
   unsigned long long wst_dh = 0, wst_cg = 0;  // this wave's arrival at two barriers (slots 14 / 15)
   stamp(sts, st, 0);
-  constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 1;  // (constant configuration: the grid)
-  const int s = blockIdx.x, tid = threadIdx.x, NS = SPEC ? NSC : (int)gridDim.x;
+  constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 1;  // (constant configuration: the slices)
+  // a role per block (CfgFlagBwd::SPLIT; blockIdx.x is scalar, so every role branch is a scalar
+  // branch): the conv role first -- blocks are dealt in index order and it is the critical one
+  constexpr bool SPLIT = SPEC && C::SPLIT != 0;
+  const int wrole = SPLIT && (int)blockIdx.x >= NSC ? 1 : 0;
+  const bool rconv = !SPLIT || wrole == 0, rw1 = !SPLIT || wrole == 1;  // (unsplit: both, constants)
+  const int s = SPLIT ? (int)blockIdx.x - wrole * NSC : (int)blockIdx.x, tid = threadIdx.x;
+  const int NS = SPEC ? NSC : (int)gridDim.x;
+  const bool blk0 = blockIdx.x == 0;  // the one block that advances the ctrl block
   const int auxm = SPEC ? aux_split(NSC) : auxm_;
   const int p0 = s * PP, p1 = min(NPOS, p0 + PP), np = p1 - p0, K = np * 32;
   const int KD = PP * 32 + 4;   // dps pitch (f32)
@@ -793,16 +851,30 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // (AUXD: dps behind the head scratch in a region of its own, so the head scratch stays
   // readable to the end of the kernel; convnet2_bwd_lds sizes the flagship's LDS for it)
   const int RB = AUXD ? HEAD_BYTES + CH * KD * 4 : max(CH * KD * 4, HEAD_BYTES);
-  float* xs = reinterpret_cast<float*>(smem);                              // [CH][XR][28]
-  float* dps = reinterpret_cast<float*>(smem + XS_BYTES + (AUXD ? HEAD_BYTES : 0));  // [CH][KD] (after the head)
-  uint16_t* pt = reinterpret_cast<uint16_t*>(smem + XS_BYTES + RB);        // [PP*32][HP]
-  uint16_t* dht = pt + PP * 32 * HP;                                       // [2][HID][HP] dh^T hi, lo
-  uint16_t* dhs = dht + 2 * HID * HP;                                      // [2][CH][HP]  dh hi, lo
-  uint16_t* w1s = dhs + 2 * CH * HP;                                       // [PP*32][HP]
-  uint8_t* cs = reinterpret_cast<uint8_t*>(w1s + PP * 32 * HP);            // [CH][KC] argmax codes
-  float* red = reinterpret_cast<float*>(pt);  // [16][320] reduction scratch, after the MFMAs
+  // byte offsets of the LDS regions.  One block per slice: xs | head (dps behind it or aliasing
+  // it) | pt | dht | dhs | w1s | cs, `red` over pt / dht and `ared` over dps once they are dead.
+  // A role per block (convnet2_bwd_role_lds sizes the same layouts; the head leads both, so
+  // every offset is a constant of the code that uses it, none a per-role select):
+  //   conv role  head | xs | dps | dhs | w1s | cs | red   (red in a region of its own: nothing
+  //              the conv gradient still reads is under it, so no barrier ahead of its stores)
+  //   W1 role    head | pt | dht | ared
+  static_assert(!SPLIT || (W16 && AUXD), "the roles build on the 16-wave mapping with dps in its own region");
+  const int PTB = PP * 32 * HP * 2, DHTB = 2 * HID * HP * 2, DHSB = 2 * CH * HP * 2, DPSB = CH * KD * 4;
+  const int o_head = SPLIT ? 0 : XS_BYTES, o_xs = SPLIT ? HEAD_BYTES : 0;
+  const int o_dps = SPLIT ? HEAD_BYTES + XS_BYTES : XS_BYTES + (AUXD ? HEAD_BYTES : 0);
+  const int o_pt = SPLIT ? HEAD_BYTES : XS_BYTES + RB, o_dht = o_pt + PTB;
+  const int o_dhs = SPLIT ? o_dps + DPSB : o_dht + DHTB, o_w1s = o_dhs + DHSB, o_cs = o_w1s + PTB;
+  const int o_red = SPLIT ? o_cs + CH * KC : o_pt, o_ared = SPLIT ? o_dht + DHTB : o_dps;
+  float* xs = reinterpret_cast<float*>(smem + o_xs);                       // [CH][XR][28]
+  float* dps = reinterpret_cast<float*>(smem + o_dps);                     // [CH][KD] (after the head)
+  uint16_t* pt = reinterpret_cast<uint16_t*>(smem + o_pt);                 // [PP*32][HP]
+  uint16_t* dht = reinterpret_cast<uint16_t*>(smem + o_dht);               // [2][HID][HP] dh^T hi, lo
+  uint16_t* dhs = reinterpret_cast<uint16_t*>(smem + o_dhs);               // [2][CH][HP]  dh hi, lo
+  uint16_t* w1s = reinterpret_cast<uint16_t*>(smem + o_w1s);               // [PP*32][HP]
+  uint8_t* cs = reinterpret_cast<uint8_t*>(smem + o_cs);                   // [CH][KC] argmax codes
+  float* red = reinterpret_cast<float*>(smem + o_red);  // [16][320] reduction scratch, after the MFMAs
   // head scratch (aliases dps unless AUXD: used before the dP MFMA of each chunk)
-  float* hs = reinterpret_cast<float*>(smem + XS_BYTES);  // [CH][HPITCH] h = relu(dense-1)
+  float* hs = reinterpret_cast<float*>(smem + o_head);  // [CH][HPITCH] h = relu(dense-1)
   float* spl = hs + CH * HPITCH;   // [716] b1[64] W2[64][10] b2[10]
   float* zs = spl + 716;           // [CH][ZP] logits, then dz
   float* rl = zs + CH * ZP;        // [CH] per-row loss
@@ -820,7 +892,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   const int chunk_aux = auxm & 0xffff, ltpe = auxm >> 16, tpe = 1 << ltpe;
   const int ae_local = tid >> ltpe, aq = tid & (tpe - 1);
   const int ae = s * chunk_aux + ae_local;
-  const bool aux_on = ae_local < chunk_aux && ae < NAUX2;
+  const bool aux_on = rw1 && ae_local < chunk_aux && ae < NAUX2;
   const int aec = min(ae, NAUX2 - 1);
   float arsum = 0.f;
 
@@ -828,7 +900,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // previous metric, b1/W2/b2, the bf16 W1 slice, chunk 0's pooled tile and argmax codes),
   // kept ahead of the ctrl load by a scheduling barrier (as in fwd) ----
   // previous step's reduced metric (sharded: fwd folds it from the small messages)
-  const float ag_old = sh ? 0.f : Gr[OFF_LOSS + max(0, min(aec - NSMALL, 2))];
+  const float ag_old = sh || !rw1 ? 0.f : Gr[OFF_LOSS + max(0, min(aec - NSMALL, 2))];
   // small parameters (b1/W2/b2, updated by fwd): 2 per thread, re-staged every chunk
   // (16 waves: one per thread, threads past the 714 load nothing)
   float spv0 = 0.f, spv1 = 0.f;
@@ -864,9 +936,16 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   constexpr int WS = W16 ? 256 : 512;
   const int wt = W16 ? tid - 768 : tid;  // (< 0: no W1 units)
   wv0 = wv1 = make_uint4(0u, 0u, 0u, 0u);
-  if (wt >= 0 && wt < n8) wv0 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[wt];
-  if ((!SPEC || WS < PP * 32 * HID / 8) && wt >= 0 && wt + WS < n8)
-    wv1 = reinterpret_cast<const uint4*>(w1bf + p0 * 32 * HID)[wt + WS];
+  // (the bf16 copy has one buffer per step parity: dP reads the live one, the eager update
+  // writes the other.  Known parity: the host passed them as w1bf / w1bf_out; else they are
+  // buffers 0 / 1 and the load waits for the ctrl block's parity.  W1 role: no bf16 slice)
+  auto load_wv = [&](const uint16_t* src) __attribute__((always_inline)) {
+    if (!rconv) return;
+    if (wt >= 0 && wt < n8) wv0 = reinterpret_cast<const uint4*>(src + p0 * 32 * HID)[wt];
+    if ((!SPEC || WS < PP * 32 * HID / 8) && wt >= 0 && wt + WS < n8)
+      wv1 = reinterpret_cast<const uint4*>(src + p0 * 32 * HID)[wt + WS];
+  };
+  if (phint >= 0) load_wv(w1bf);
   // the body -- pooled tile, argmax codes, input rows, read only by the MFMAs and the conv
   // gradient -- is staged by NB threads with two slots each: all 512 when chunked; in the
   // single-chunk step only waves 4-7 (slots bt and bt + 256), which have no logits to
@@ -877,7 +956,9 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   const int bt = ONE ? tid - 256 : tid;  // (< 0: no body slots)
   const bool bw = !ONE || (bt >= 0 && bt < NB);
   const int ct = W16 ? tid - 768 : bt;   // code slot
-  const bool cw = W16 ? ct >= 0 : bw;
+  // (a role per block: the pooled tile is the W1 role's, the codes and the input rows the conv role's)
+  const bool bwp = bw && rw1, bwx = bw && rconv;
+  const bool cw = (W16 ? ct >= 0 : bw) && rconv;
   XStage<U8> xst, xst1;      // input rows: slot bt, and (single chunk, 8 waves) bt + 256
   uint4 pv0, pv1, pv2, pv3;  // pooled tile units bt + j NB (K * 8 <= 1024 units)
   uint4 cv, cv1;             // argmax codes, units ct (+ NB), zeroed at the LDS store unless cok
@@ -915,7 +996,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     if (i < CH * kc) v = *reinterpret_cast<const uint4*>(code + (__umul24(min(lb, B - 1), FEAT) + p0 * NF + q * 16));
   };
   auto load_indep = [&](int chunk) __attribute__((always_inline)) {
-    if (bw) {
+    if (bwp) {
       load_pv(pv0, bt, chunk);
       if (NPV > 1) load_pv(pv1, bt + NB, chunk);
       if (ONE && NPV > 2) {
@@ -931,7 +1012,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       const int b = chunk * CH + min(tid, CH - 1);
       ylab = ycur[min(b, B - 1)];
       yval = tid < CH && b < B && ylab >= 0;
-      if (bw) {
+      if (bwx) {
         x_load<U8>(xst, xcur, chunk * CH, B, B - chunk * CH, LG_CH, r0, nrows, bt);
         if (ONE && !W16) x_load<U8>(xst1, xcur, chunk * CH, B, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
       }
@@ -942,10 +1023,17 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
 
   const Ctrl c = *ctrl;
   const int cur = c.cur2, par = phint >= 0 ? phint : c.par2;
-  if (phint >= 0 && phint != c.par2 && s == 0 && tid == 0)
+  if (phint >= 0 && phint != c.par2 && blk0 && tid == 0)
     __hip_atomic_fetch_or(&ctrl->bad, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // parity unknown to the host: w1bf / w1bf_out are buffers 0 / 1, the live one is `par`
+  if (phint < 0 && par) {
+    const uint16_t* live = w1bf_out;
+    w1bf_out = const_cast<uint16_t*>(w1bf);
+    w1bf = live;
+  }
+  if (phint < 0) load_wv(w1bf);
   const unsigned xe = (unsigned)c.xcnt2 + 1u;  // sharded: this step's exchange epoch
-  if (s == 0 && tid == 0) {
+  if (blk0 && tid == 0) {
     ctrl->cursor = next_cursor(c, cur);
     ctrl->iterations = c.iterations + 1;
     ctrl->wpar = c.wpar ^ 1;  // fwd of this step wrote the next W1 buffer
@@ -962,7 +1050,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   constexpr int UPI = U8 ? NPIX / 16 : NPIX / 4;  // 16-byte units per image
   // (a block's 512 units sit on threads 0-511, as does its share of the dead hacc parity)
   const int xpu = s * 512 + tid;
-  const bool xpf = ONE && xnext != nullptr && (!W16 || tid < 512) && xpu < B * UPI;
+  const bool xpf = ONE && rw1 && xnext != nullptr && (!W16 || tid < 512) && xpu < B * UPI;
   uint4 xnv = make_uint4(0u, 0u, 0u, 0u);
 
   // then the ctrl-dependent ones: the dense-1 sums by parity (unless known), the labels and
@@ -976,7 +1064,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         yval = tid < CH && b < B && g < c.nsamples;
         ylab = labels[max(0L, min(g, (long)c.nsamples - 1))];
       }
-      if (bw) {
+      if (bwx) {
         x_load<U8>(xst, X, row_base + chunk * CH, c.nsamples, B - chunk * CH, LG_CH, r0, nrows, bt);
         if (ONE && !W16) x_load<U8>(xst1, X, row_base + chunk * CH, c.nsamples, B - chunk * CH, LG_CH, r0, nrows, bt + NB);
       }
@@ -1015,15 +1103,18 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       store_cv(cv, cok, ct);
       if (ONE && !W16 && (!SPEC || NB < CH * KCM)) store_cv(cv1, cok1, ct + NB);
     }
-    if (!bw) return;
-    store_pv(pv0, bt);
-    if (NPV > 1) store_pv(pv1, bt + NB);
-    if (ONE && NPV > 2) {
-      store_pv(pv2, bt + 2 * NB);
-      store_pv(pv3, bt + 3 * NB);
+    if (bwp) {
+      store_pv(pv0, bt);
+      if (NPV > 1) store_pv(pv1, bt + NB);
+      if (ONE && NPV > 2) {
+        store_pv(pv2, bt + 2 * NB);
+        store_pv(pv3, bt + 3 * NB);
+      }
     }
-    x_store<U8>(xst, xs, LG_CH, nrows);
-    if (ONE && !W16) x_store<U8>(xst1, xs, LG_CH, nrows);
+    if (bwx) {
+      x_store<U8>(xst, xs, LG_CH, nrows);
+      if (ONE && !W16) x_store<U8>(xst1, xs, LG_CH, nrows);
+    }
   };
   auto store_chunk = [&](int chunk) __attribute__((always_inline)) {
     store_body();
@@ -1040,8 +1131,8 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // (w1s is read only by the dP MFMAs, several barriers later)
   // (constant configuration: every row of the tile is written, rows past K as the zeros held)
   const int n8s = SPEC ? PP * 32 * HID / 8 : n8;
-  if (wt >= 0 && wt < n8s) *reinterpret_cast<uint4*>(w1s + (wt >> 3) * HP + (wt & 7) * 8) = wv0;
-  if (wt >= 0 && wt + WS < n8s) *reinterpret_cast<uint4*>(w1s + ((wt + WS) >> 3) * HP + (wt & 7) * 8) = wv1;
+  if (rconv && wt >= 0 && wt < n8s) *reinterpret_cast<uint4*>(w1s + (wt >> 3) * HP + (wt & 7) * 8) = wv0;
+  if (rconv && wt >= 0 && wt + WS < n8s) *reinterpret_cast<uint4*>(w1s + ((wt + WS) >> 3) * HP + (wt & 7) * 8) = wv1;
 
   // dW1 / dP tiles of the wave: 8 waves, tile rows dm0 + 2 i (one per position i); 16 waves,
   // the one tile row dm0 = wave >> 2 (position dm0 >> 1)
@@ -1113,7 +1204,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     stamp(sts, st, 1);
     // eager: the slice's fp32 masters / velocities for the update right after the dW1
     // MFMAs, issued once the staged operands have landed (in flight through the head)
-    if (ONE && eager) {
+    if (ONE && eager && rw1) {
 #pragma unroll
       for (int i = 0; i < TPW; ++i) {
         const int mt = W16 ? dm0 : dm0 + 2 * i, pi = W16 ? dm0 >> 1 : i;  // tile row, its position
@@ -1243,14 +1334,18 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         dsum += d;
         hi[j] = f2bf(d);
         lo[j] = bf16_lo(d, hi[j]);
-        dhs[(rb + j) * HP + n] = hi[j];
-        dhs[CH * HP + (rb + j) * HP + n] = lo[j];
+        if (rconv) {  // (a role per block: only the layout the role's MFMAs read)
+          dhs[(rb + j) * HP + n] = hi[j];
+          dhs[CH * HP + (rb + j) * HP + n] = lo[j];
+        }
       }
-      *reinterpret_cast<uint2*>(dht + n * HP + rb) =
-          make_uint2((uint32_t)hi[0] | ((uint32_t)hi[1] << 16), (uint32_t)hi[2] | ((uint32_t)hi[3] << 16));
-      *reinterpret_cast<uint2*>(dht + HID * HP + n * HP + rb) =
-          make_uint2((uint32_t)lo[0] | ((uint32_t)lo[1] << 16), (uint32_t)lo[2] | ((uint32_t)lo[3] << 16));
-      db1p[(4 * mt + kq) * HID + n] = dsum;  // [16][64]: partial over rows rb .. rb + 3
+      if (rw1) {
+        *reinterpret_cast<uint2*>(dht + n * HP + rb) =
+            make_uint2((uint32_t)hi[0] | ((uint32_t)hi[1] << 16), (uint32_t)hi[2] | ((uint32_t)hi[3] << 16));
+        *reinterpret_cast<uint2*>(dht + HID * HP + n * HP + rb) =
+            make_uint2((uint32_t)lo[0] | ((uint32_t)lo[1] << 16), (uint32_t)lo[2] | ((uint32_t)lo[3] << 16));
+        db1p[(4 * mt + kq) * HID + n] = dsum;  // [16][64]: partial over rows rb .. rb + 3
+      }
     }
     if (st != nullptr) wst_dh = __builtin_amdgcn_s_memrealtime();  // (this wave's arrival at the dh barrier)
     lds_barrier();
@@ -1263,6 +1358,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     // dW1[k][n] += sum_b P[b][k] (dh_hi + dh_lo)[b][n]
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
+      if (!rw1) break;
       const int mt = W16 ? dm0 : dm0 + 2 * i;
       if ((W16 ? dm0 >> 1 : i) >= npl) break;
 #pragma unroll
@@ -1278,9 +1374,10 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     // the stores have drained, after the conv gradient) and travels during dP / conv grad
     if (ONE && sh) push_partials();
     // eager: the slice's SGD update now, its stores overlapping dP and the conv gradient
-    // (fp32 master and velocity in place, bf16 copy for the next fwd; this block read its
-    // old bf16 slice in the prologue and nobody else touches the slice in this launch)
-    if (ONE && eager) {
+    // (fp32 master and velocity in place: only this block touches the slice's masters in this
+    // launch; the bf16 copy for the next fwd goes to the buffer of the other parity, which no
+    // block of this launch reads -- the slice's conv-role block reads the live one)
+    if (ONE && eager && rw1) {
 #pragma unroll
       for (int i = 0; i < TPW; ++i) {
         const int mt = W16 ? dm0 : dm0 + 2 * i, pi = W16 ? dm0 >> 1 : i;
@@ -1300,8 +1397,9 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         }
       }
     }
+    if (SPLIT && !rconv) stamp(sts, st, 3);  // (W1 role: update stored -- its stores issued)
     // dP[b][k] = sum_n (dh_hi + dh_lo)[b][n] W1[k][n]
-    {
+    if (rconv) {
       const int pm = wave & 3;
 #pragma unroll
       for (int i = 0; i < TPW; ++i) {
@@ -1322,6 +1420,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     }
     if (C::AUX == 1) aux_sums();  // (behind the MFMAs and the dP stores, nothing waits for it)
     if (st != nullptr) wst_cg = __builtin_amdgcn_s_memrealtime();  // (arrival at the pre-conv-gradient barrier)
+    if (SPLIT && !rconv) break;  // (W1 role: no dps, no conv gradient; single chunk)
     lds_barrier();
     stamp(sts, st, 3);
     // MaxPool + ReLU backward fused into the conv weight-gradient accumulation: taps T0 .. T1 - 1
@@ -1368,18 +1467,22 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       G[OFF_W1 + (unsigned)((p0 * 32 + k) * HID + 16 * dn + lr16)] = accw[i][j];
     }
   }
-  lds_barrier();  // pt/dht region becomes `red`, dps becomes `ared`
+  // pt/dht region becomes `red`, dps becomes `ared` (a role per block: both have regions of
+  // their own, which nothing read since the last barrier lies under)
+  if (!SPLIT) lds_barrier();
   // (16 waves: each half writes the taps it accumulated; red holds the same values either way)
+  if (rconv) {
 #pragma unroll
-  for (int t = 0; t < 9; ++t)
-    if (!W16 || half == (t >= 5 ? 1 : 0)) red[grp * NCONV + t * NF + ch] = gw[t];
-  if (!W16 || half == 1) red[grp * NCONV + OFF_BC + ch] = gb;
-  float* ared = dps;
-  if (!W16 || tid < 512) ared[tid] = arsum;  // (aux_split maps 512 threads)
+    for (int t = 0; t < 9; ++t)
+      if (!W16 || half == (t >= 5 ? 1 : 0)) red[grp * NCONV + t * NF + ch] = gw[t];
+    if (!W16 || half == 1) red[grp * NCONV + OFF_BC + ch] = gb;
+  }
+  float* ared = reinterpret_cast<float*>(smem + o_ared);
+  if (rw1 && (!W16 || tid < 512)) ared[tid] = arsum;  // (aux_split maps 512 threads)
   lds_barrier();
   // this slice's conv-gradient partial, fixed order over the 16 thread groups, then a
   // 64-bit fixed-point atomic add (order-independent sum over the slices)
-  for (int i = tid; i < (cprobe ? 0 : NCONV); i += NT) {
+  for (int i = tid; i < (cprobe || !rconv ? 0 : NCONV); i += NT) {
     float a = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) a += red[r * NCONV + i];
@@ -1407,12 +1510,12 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   // spread over the blocks
   {
     long long* hz = hacc + (long)(par ^ 1) * B * HACC_PITCH;
-    if (!W16 || tid < 512)
+    if (rw1 && (!W16 || tid < 512))
       for (int i = s * 512 + tid; i < B * HID / 2; i += NS * 512)  // (32 16-B units per row)
         *reinterpret_cast<uint4*>(hz + (i >> 5) * HACC_PITCH + (i & 31) * 2) = make_uint4(0u, 0u, 0u, 0u);
   }
   if (xpf) reinterpret_cast<uint4*>(xnext)[xpu] = xnv;
-  if (ONE && xnext != nullptr && s == 0 && tid == 0) *xtag = ((long long)c.xgen << 32) | (long long)(unsigned)(ncur + 1);
+  if (ONE && rw1 && xnext != nullptr && s == 0 && tid == 0) *xtag = ((long long)c.xgen << 32) | (long long)(unsigned)(ncur + 1);
   if (C::SH && sh) exchange_tail(xa, ctrl, G, hconv + par * NCONV, accw, xe, s, NS, np, p0, dn, dm0, lane, tid, xown, xo, xu);
   stamp(sts, st, 5);
   stamp_flush(sts, st, 13);
@@ -1446,8 +1549,9 @@ __global__ __launch_bounds__(512) void bwd(long long* __restrict__ hacc, const i
 }
 
 // The flagship configuration (CfgFlagBwd, single chunk): no packed sizes, no exchange
-// arguments; the aux split follows from the constant grid.  The preloaded dwords are the
-// same pointers as above and the parity hint.
+// arguments; the aux split follows from the constant slicing.  The preloaded dwords are the
+// same pointers as above and the parity hint.  Grid CfgFlagBwd::GRID: one block per slice, or
+// (SPLIT) two, a role each.  w1bf / w1bf_out: the bf16 W1 pair (see CfgFlagBwd).
 template <bool U8>
 __global__ __launch_bounds__(CfgFlagBwd::NT) void bwd_flag(long long* __restrict__ hacc, const int* __restrict__ ycur,
                                                 const void* __restrict__ xcur, const float* P, const uint16_t* w1bf,
@@ -1473,8 +1577,12 @@ __global__ __launch_bounds__(1024) void flush(float* __restrict__ P, float* __re
                                              long long* __restrict__ hconv, const float* __restrict__ calt,
                                              long long* __restrict__ hacc, int B, int eager,
                                              uint16_t* __restrict__ w1bf, Ctrl* __restrict__ ctrl,
-                                             long long* __restrict__ hconv_w) {
+                                             long long* __restrict__ hconv_w, int phint) {
+  // w1bf: buffer 0 of the bf16 copy -- the live one from here on (the parity returns to 0).
+  // Eager: nothing here writes it; w1bf_live0 ran first unless the host knew the parity to be 0
   const Ctrl c = *ctrl;
+  if (phint >= 0 && phint != c.wpar && blockIdx.x == 0 && threadIdx.x == 0)  // (as in the step kernels)
+    __hip_atomic_fetch_or(&ctrl->bad, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const bool mom = c.momentum != 0.f, pend = c.pending != 0;
   // after a step's bwd: current W1 / conv parameters live in the alternates when wpar is
   // set; the pending conv gradient is in hconv[wpar ^ 1]
@@ -1534,6 +1642,17 @@ __global__ __launch_bounds__(1024) void flush(float* __restrict__ P, float* __re
       ctrl->ticket = 0;  // (the sharded bwd's arrival count: bounded between flushes)
     }
   }
+}
+
+// Eager update, ahead of flush: the live bf16 W1 buffer is the ctrl block's parity; flush
+// returns the parity to 0, so after an odd number of steps buffer 1 is copied over buffer 0
+// (nothing to do at parity 0: the launch is skipped when the host knows that).  16 bytes per
+// thread, FEAT * HID / 8 units.
+__global__ __launch_bounds__(512) void w1bf_live0(const Ctrl* __restrict__ ctrl, const uint4* __restrict__ b1,
+                                                  uint4* __restrict__ b0) {
+  if (ctrl->wpar == 0) return;
+  const int i = blockIdx.x * 512 + threadIdx.x;
+  if (i < FEAT * HID / 8) b0[i] = b1[i];
 }
 
 // =================================================================================
@@ -1600,8 +1719,27 @@ size_t convnet2_fwd_lds(int PP, int lg) {
 }
 // flagship: the layout of bwd_flag (CfgFlagBwd::AUX: dps in a region of its own behind the head
 // scratch instead of aliasing it)
+// LDS bytes one role of the flagship backward needs (CfgFlagBwd::SPLIT; role 0 conv, 1 W1):
+// the layouts of bwd_body
+//   conv role  head | xs | dps | dhs | w1s | cs | red
+//   W1 role    head | pt | dht | ared (one float per aux thread)
+size_t convnet2_bwd_role_lds(int PP, int role) {
+  using namespace convnet;
+  const size_t head = (size_t)convnet2::HEAD_BYTES, tile = (size_t)PP * 32 * HP * 2, slack = 16 + 256 * 4;
+  if (role == 0)
+    return head + XS_BYTES + (size_t)CH * (PP * 32 + 4) * 4 + (size_t)2 * CH * HP * 2 + tile + (size_t)CH * PP * 32 +
+           (size_t)16 * NCONV * 4 + slack;
+  return head + tile + (size_t)2 * HID * HP * 2 + (size_t)512 * 4 + slack;
+}
+int convnet2_bwd_flag_blocks() { return convnet2::CfgFlagBwd::GRID; }
+int convnet2_bwd_flag_split() { return convnet2::CfgFlagBwd::SPLIT; }
+
 size_t convnet2_bwd_lds(int PP, bool flagship) {
   using namespace convnet;
+  if (flagship && convnet2::CfgFlagBwd::SPLIT != 0) {  // one launch: the larger of the two roles
+    const size_t a = convnet2_bwd_role_lds(PP, 0), b = convnet2_bwd_role_lds(PP, 1);
+    return a > b ? a : b;
+  }
   const int KD = PP * 32 + 4;
   const size_t dpsb = (size_t)CH * KD * 4;
   const size_t rb = flagship && convnet2::CfgFlagBwd::AUX != 0 ? (size_t)convnet2::HEAD_BYTES + dpsb
@@ -1631,8 +1769,24 @@ static int ppb_of(const ConvNetBuffers& b, int PP) { return b.ppb > 0 ? b.ppb : 
 bool convnet2_specialised(const ConvNetBuffers& b, int B, int PP) {
   using namespace convnet;
   using namespace convnet2;
+  // (a role per block: the conv block of a slice reads the bf16 W1 slice its W1 block rewrites,
+  // so the two parity buffers of the copy must be distinct)
+  const bool two = b.w1bf_alt != nullptr && b.w1bf_alt != b.w1bf;
   return !b.force_generic && !b.xa && !b.Gr && !b.hconv_r && B == CH && PP == CfgFlagFwd::PP &&
-         convnet_f1_lg(B) == CfgFlagFwd::LG && ppb_of(b, PP) == CfgFlagBwd::PP && eager2(b, B) == 1;
+         convnet_f1_lg(B) == CfgFlagFwd::LG && ppb_of(b, PP) == CfgFlagBwd::PP && eager2(b, B) == 1 &&
+         (two || CfgFlagBwd::SPLIT == 0);
+}
+
+// The bf16 W1 copy as the step kernels take it (see CfgFlagBwd): (live, other) by the parity
+// hint, or (buffer 0, buffer 1) when the host does not know the parity.  One buffer only
+// (w1bf_alt null): both are that buffer -- the in-place copy of one block per slice.
+struct W1bfPair {
+  uint16_t* live;
+  uint16_t* other;
+};
+static W1bfPair w1bf_pair(const ConvNetBuffers& b) {
+  uint16_t* alt = b.w1bf_alt ? b.w1bf_alt : b.w1bf;
+  return b.par_hint == 1 ? W1bfPair{alt, b.w1bf} : W1bfPair{b.w1bf, alt};
 }
 
 template <bool U8>
@@ -1641,17 +1795,18 @@ static void launch2_fwd(const ConvNetBuffers& b, int B, int PP, hipStream_t st) 
   const int NS = convnet_num_slices(PP);
   const int lg = convnet_f1_lg(B);
   const dim3 g1(NS, (B + (1 << lg) - 1) >> lg);
+  const W1bfPair w1 = w1bf_pair(b);
   if (convnet2_specialised(b, B, PP)) {
     hipLaunchKernelGGL((convnet2::fwd_flag<U8>), g1, dim3(convnet2::CfgFlagFwd::NT), convnet2_fwd_lds(PP, lg), st,
-                       b.xnext, b.xtag, b.w1bf, b.P, b.V, b.calt, b.hconv, b.G, b.ctrl, b.X, b.pooled, b.code, b.hacc,
-                       b.hconv, b.stamps, b.labels, b.xcur, b.ycur, b.par_hint);
+                       b.xnext, b.xtag, w1.live, b.P, b.V, b.calt, b.hconv, b.G, b.ctrl, b.X, b.pooled, b.code, b.hacc,
+                       b.hconv, b.stamps, b.labels, b.xcur, b.ycur, b.par_hint, w1.other);
     return;
   }
   hipLaunchKernelGGL((convnet2::fwd<U8>), g1, dim3(512), convnet2_fwd_lds(PP, lg), st,
-                     B <= CH ? b.xnext : nullptr, b.w1bf, b.P, b.V, b.calt, b.hconv_r ? b.hconv_r : b.hconv,
+                     B <= CH ? b.xnext : nullptr, w1.live, b.P, b.V, b.calt, b.hconv_r ? b.hconv_r : b.hconv,
                      b.Gr ? b.Gr : b.G, B | (PP << 16), lg | (eager2(b, B) << 8), b.ctrl, b.X, b.W1alt, b.V1alt,
                      b.pooled, b.code, b.hacc, b.hconv, b.stamps, xargs(b), b.xtag, b.labels,
-                     B <= CH ? b.xcur : nullptr, b.ycur, b.par_hint);
+                     B <= CH ? b.xcur : nullptr, b.ycur, b.par_hint, w1.other);
 }
 
 template <bool U8>
@@ -1662,20 +1817,21 @@ static void launch2_bwd(const ConvNetBuffers& b, int B, int PPf, hipStream_t st)
   // aux elements (b1/W2/b2 gradients + metric tail) per block, and a power-of-two thread
   // count per element (<= 64) that fits them in 512 threads
   const int auxm = convnet2::aux_split(NS);
+  const W1bfPair w1 = w1bf_pair(b);
   if (convnet2_specialised(b, B, PPf))
-    hipLaunchKernelGGL((convnet2::bwd_flag<U8>), dim3(NS), dim3(convnet2::CfgFlagBwd::NT), convnet2_bwd_lds(PP, true), st, b.hacc, b.ycur, b.xcur,
-                       b.P, b.w1bf, b.pooled, b.code, b.par_hint, b.G, b.ctrl, b.X, b.labels, b.G, b.hconv, b.P, b.V,
-                       b.w1bf, b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.xnext, b.xtag);
+    hipLaunchKernelGGL((convnet2::bwd_flag<U8>), dim3(convnet2::CfgFlagBwd::GRID), dim3(convnet2::CfgFlagBwd::NT), convnet2_bwd_lds(PP, true), st, b.hacc, b.ycur, b.xcur,
+                       b.P, w1.live, b.pooled, b.code, b.par_hint, b.G, b.ctrl, b.X, b.labels, b.G, b.hconv, b.P, b.V,
+                       w1.other, b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.xnext, b.xtag);
   else if (B <= CH)
     hipLaunchKernelGGL((convnet2::bwd<U8, true>), dim3(NS), dim3(512), convnet2_bwd_lds(PP), st, b.hacc,
                        B <= CH ? b.ycur : nullptr, B <= CH ? b.xcur : nullptr, b.par_hint, B | (PP << 16), b.P,
-                       b.w1bf, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, b.w1bf,
+                       w1.live, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, w1.other,
                        b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.Gr ? b.Gr : b.G, xargs(b), b.xnext, b.xtag,
                        auxm);
   else
     hipLaunchKernelGGL((convnet2::bwd<U8, false>), dim3(NS), dim3(512), convnet2_bwd_lds(PP), st, b.hacc,
                        B <= CH ? b.ycur : nullptr, B <= CH ? b.xcur : nullptr, b.par_hint, B | (PP << 16), b.P,
-                       b.w1bf, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, b.w1bf,
+                       w1.live, b.pooled, b.code, b.ctrl, b.X, b.labels, b.G, b.hconv, eager2(b, B), b.P, b.V, w1.other,
                        b.stamps ? b.stamps + 2 * 256 * 16 : nullptr, b.Gr ? b.Gr : b.G, xargs(b), b.xnext, b.xtag,
                        auxm);
 }
@@ -1692,6 +1848,10 @@ hipError_t convnet2_fwd_compiled_threads(const ConvNetBuffers& b, int B, int PP,
   const hipError_t e = hipFuncGetAttributes(&at, f);
   if (e == hipSuccess) *out = at.maxThreadsPerBlock;
   return e;
+}
+
+int convnet2_bwd_blocks(const ConvNetBuffers& b, int B, int PP) {
+  return convnet2_specialised(b, B, PP) ? convnet2::CfgFlagBwd::GRID : convnet_num_slices(ppb_of(b, PP));
 }
 
 int convnet2_bwd_threads(const ConvNetBuffers& b, int B, int PP) {
@@ -1740,9 +1900,13 @@ hipError_t convnet2_launch_gather(const ConvNetBuffers& b, int PP, hipStream_t s
 }
 
 hipError_t convnet2_launch_flush(const ConvNetBuffers& b, int B, hipStream_t st) {
+  // eager: buffer 0 of the bf16 W1 copy becomes the live one (flush returns the parity to 0)
+  if (eager2(b, B) && b.w1bf_alt && b.w1bf_alt != b.w1bf && b.par_hint != 0)
+    hipLaunchKernelGGL(convnet2::w1bf_live0, dim3((convnet::FEAT * convnet::HID / 8 + 511) / 512), dim3(512), 0, st, b.ctrl,
+                       reinterpret_cast<const uint4*>(b.w1bf_alt), reinterpret_cast<uint4*>(b.w1bf));
   hipLaunchKernelGGL(convnet2::flush, dim3(eager2(b, B) ? 1 : 340), dim3(eager2(b, B) ? 1024 : 256), 0, st, b.P, b.Gr ? b.Gr : b.G, b.V,
                      b.W1alt, b.V1alt, b.hconv_r ? b.hconv_r : b.hconv, b.calt, b.hacc, B, eager2(b, B), b.w1bf, b.ctrl,
-                     b.hconv);
+                     b.hconv, b.par_hint);
   return hipGetLastError();
 }
 

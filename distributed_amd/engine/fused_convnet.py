@@ -128,7 +128,12 @@ class FusedConvNetEngine(Engine):
         self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
         self.w1alt = torch.zeros(FEAT * HID, **f32)   # W1 double buffer (by step parity)
         self.v1alt = torch.zeros(FEAT * HID, **f32)
-        self.w1bf = torch.zeros(FEAT * HID, dtype=torch.bfloat16, device=dev)
+        # bf16 copy of W1, one buffer per step parity: a step reads the buffer of its parity,
+        # the eager update in bwd writes the other one (convnet.h); `w1bf` is the live one.
+        # Two allocations of 0.7 MB, not one of 1.4 MB: as one tensor (a request above 1 MB,
+        # which the caching allocator serves from other segments) the forward kernel measured
+        # 0.4 us longer; why was not established (BENCH.md, round 11)
+        self.w1bf_bufs = tuple(torch.zeros(FEAT * HID, dtype=torch.bfloat16, device=dev) for _ in range(2))
         self.pooled = torch.zeros(FEAT, BP, dtype=torch.bfloat16, device=dev)
         self.code = torch.zeros(B, FEAT, dtype=torch.uint8, device=dev)
         self.hacc = torch.zeros(C.convnet_hacc_elems(B), dtype=torch.int64, device=dev)  # by step parity
@@ -166,7 +171,8 @@ class FusedConvNetEngine(Engine):
         bufs = dict(params=self.P.data_ptr(), grads=self.G.data_ptr(), velocity=self.V.data_ptr(),
                     ctrl=self.ctrl.data_ptr(),
                     pooled=self.pooled.data_ptr(), code=self.code.data_ptr(), w1alt=self.w1alt.data_ptr(),
-                    v1alt=self.v1alt.data_ptr(), w1bf=self.w1bf.data_ptr(),
+                    v1alt=self.v1alt.data_ptr(), w1bf=self.w1bf_bufs[0].data_ptr(),
+                    w1bf_alt=self.w1bf_bufs[1].data_ptr(),
                     hacc=self.hacc.data_ptr(), hconv=self.hconv.data_ptr(), calt=self.calt.data_ptr(),
                     ppb=self.PPB)
         if self.xnext is not None:
@@ -631,10 +637,17 @@ class FusedConvNetEngine(Engine):
             opt.slots["momentum"].copy_(self.V[:NPARAM])
         torch.cuda.synchronize(self.device)
 
+    @property
+    def w1bf(self):
+        """The live bf16 copy of W1: the buffer of the parity the next forward reads."""
+        return self.w1bf_bufs[self.trainer.parity]
+
     def _refresh_w1bf(self):
-        """bf16 copy of W1 from the fp32 master (the eager step's fwd reads only the copy)."""
+        """bf16 copy of W1 from the fp32 master (the eager step's fwd reads only the copy):
+        both parity buffers, so whichever the next forward reads is current."""
         torch.cuda.synchronize(self.device)
-        self.w1bf.copy_(self.P[NCONV:NCONV + FEAT * HID])
+        for buf in self.w1bf_bufs:
+            buf.copy_(self.P[NCONV:NCONV + FEAT * HID])
         torch.cuda.synchronize(self.device)
 
     def after_external_write(self):

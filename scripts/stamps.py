@@ -33,18 +33,35 @@ def main():
     eng.sync()
     st = eng.stamps.cpu().numpy()
     NS = eng.trainer.num_slices
-    grids = {"fwd": (0, NS * ((B + 15) // 16)), "bwd": (2, eng.trainer.num_slices_bwd)}
+    # a role per block in the flagship backward (CfgFlagBwd::SPLIT): blocks 0 .. NSB - 1 are the
+    # conv role, NSB .. 2 NSB - 1 the W1 role; both are reported against the kernel's first block
+    NSB, nblk = eng.trainer.num_slices_bwd, eng.trainer.bwd_blocks
+    grids = {"fwd": (0, 0, NS * ((B + 15) // 16))}
+    if nblk == 2 * NSB:
+        grids["bwd conv role"] = (2, 0, NSB)
+        grids["bwd W1 role"] = (2, NSB, 2 * NSB)
+    else:
+        grids["bwd"] = (2, 0, nblk)
     names = {"fwd": ["start", "loads+sgd", "xs staged", "conv done", "atomics issued", "conv setup", "conv pool",
                      "pooled/code out", "dense-1 mfma", "dense-1 barrier"],
              "bwd": ["start", "loads staged", "head done", "mfma", "convgrad", "end", "h", "softmax", "dh",
                      "logit operands", "logit mfma+max/sum", "lse/argmax", "w0 softmax stored",
                      "w4 body stored"]}
+    names["bwd conv role"] = names["bwd"]
+    # the W1 role has no dP / conv gradient: slot 3 is stamped once its update stores are issued,
+    # slot 4 behind its aux sums
+    names["bwd W1 role"] = [{"mfma": "update stored", "convgrad": "aux sums"}.get(nm, nm) for nm in names["bwd"]]
     t0 = None
-    for kn, (k, n) in grids.items():
-        a = st[k, :n].astype(np.int64)
-        base = a[:, 0][a[:, 0] > 0].min()
+    for kn, (k, lo, hi) in grids.items():
+        a = st[k, lo:hi].astype(np.int64)
+        n = hi - lo
+        # (the roles share one launch: both against the launch's earliest block)
+        allb = st[k, :(nblk if k == 2 else hi), 0].astype(np.int64)
+        base = allb[allb > 0].min()
         t0 = base if t0 is None else t0
-        print(f"{kn}: grid {n}, first block start at +{(base - t0) / 100:.2f} us")
+        own = a[:, 0][a[:, 0] > 0]
+        print(f"{kn}: {n} blocks, first block of the launch at +{(base - t0) / 100:.2f} us, these blocks start "
+              f"median +{statistics.median((own - base) / 100.0):.2f} max +{(own.max() - base) / 100:.2f} us")
         for j, nm in enumerate(names[kn]):
             col = a[:, j]
             col = col[col > 0]
@@ -54,7 +71,7 @@ def main():
             print(f"   {j} {nm:14s} median {statistics.median(d):7.2f}  min {d.min():7.2f}  max {d.max():7.2f} us")
         if kn == "fwd":
             per_wave(a)
-        else:
+        elif kn != "bwd W1 role":  # (slot 15 is the conv role's pre-conv-gradient barrier)
             per_wave_bwd(a)
 
 
