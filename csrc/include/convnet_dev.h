@@ -291,6 +291,26 @@ __device__ __forceinline__ void conv_pool(const ConvFrag& f, const float* xs, in
       conv_tile<true>(f, xs, p0, r0, lg, nfull + (ht >> 1), ht & 1, lane, emit);
 }
 
+// ---- argmax codes pre-decoded for the conv gradient ------------------------------------
+// The backward's conv gradient needs of a code cd = arg | on << 2 (conv_tile) the byte offset
+// of the window's argmax pixel, ((cd >> 1) & 1) * IMG * 4 + (cd & 1) * 4, and the ReLU mask.
+// Decoded per (image, position) pair in the gradient loop that was ~12 VALU instructions in a
+// VALU-issue-bound phase; the waves that stage the codes translate them once instead, into a
+// 16-bit entry per code: low byte the offset (0, 4, 112, 116), high byte 0xFF when the unit
+// was on, 0x00 when off -- read back as an unsigned and a signed byte, the offset and an
+// all-ones / zero mask arrive without any decoding.  Four codes (one word) take four byte
+// permutes: two table look-ups with the code bytes as selectors, two interleaves.
+constexpr int CGE_BYTES = 2;  // bytes per entry
+constexpr uint32_t CGE_OFFS = (4u << 8) | ((uint32_t)(IMG * 4) << 16) | ((uint32_t)(IMG * 4 + 4) << 24);
+static_assert(IMG * 4 + 4 < 256, "entry offsets fit a byte");
+__device__ __forceinline__ void code_entries(uint32_t w, uint32_t& e01, uint32_t& e23) {
+  const uint32_t sel = w & 0x07070707u;  // (only bits 0-2 of a code mean anything)
+  const uint32_t offs = __builtin_amdgcn_perm(CGE_OFFS, CGE_OFFS, sel);  // codes 4-7: the offsets of 0-3
+  const uint32_t mask = __builtin_amdgcn_perm(0xffffffffu, 0u, sel);     // codes 4-7: on
+  e01 = __builtin_amdgcn_perm(mask, offs, 0x05010400u);
+  e23 = __builtin_amdgcn_perm(mask, offs, 0x07030602u);
+}
+
 // ---- fixed-point cross-block sums, DPP row reductions, small MFMA, SGD-or-keep ----------
 constexpr float HSCALE = 4294967296.f;          // 2^32
 constexpr double HINV = 1.0 / 4294967296.0;
@@ -319,6 +339,36 @@ __device__ __forceinline__ long long to_fix(float v, float scale, int* bad) {
 __device__ __forceinline__ float from_fix(long long q, double inv) {
   const float fi = (float)inv;
   return fmaf((float)(q >> 24), fi * 16777216.f, (float)(int)(q & 0xFFFFFF) * fi);
+}
+// The same value without the 64-bit conversion.  hipcc expands (float)(int64) into ~13 VALU
+// instructions, two 64-bit shifts among them, per value; when q >> 24 fits an int32 --
+// |q| < 2^55: every dense-1 sum and conv gradient short of divergence -- that high part is one
+// v_alignbit_b32 and converts with v_cvt_f32_i32 to the same correctly rounded float.
+// fix_narrow: bits 63 .. 55 of q are copies of one sign bit.
+__device__ __forceinline__ bool fix_narrow(long long q) {
+  return (unsigned)(((int)(q >> 32) >> 23) + 1) < 2u;
+}
+__device__ __forceinline__ float from_fix_narrow(long long q, double inv) {
+  const float fi = (float)inv;
+  const int h = (int)__builtin_amdgcn_alignbit((uint32_t)((unsigned long long)q >> 32), (uint32_t)q, 24);
+  return fmaf((float)h, fi * 16777216.f, (float)(int)((uint32_t)q & 0xFFFFFFu) * fi);
+}
+// N values per lane: the narrow form when every value of every lane of the wave fits (one
+// ballot, a scalar branch), else from_fix as it stands -- for every int64 the bits of from_fix.
+// (A per-lane select between the two forms compiles back into the 64-bit sequence.)  Call it
+// where whole waves arrive together (the ballot covers the active lanes).
+template <int N>
+__device__ __forceinline__ void from_fix_wave(float (&out)[N], const long long (&q)[N], double inv) {
+  bool wide = false;
+#pragma unroll
+  for (int i = 0; i < N; ++i) wide |= !fix_narrow(q[i]);
+  if (__builtin_amdgcn_ballot_w64(wide) == 0ull) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = from_fix_narrow(q[i], inv);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = from_fix(q[i], inv);
+  }
 }
 
 __device__ __forceinline__ void atomic_add_i64(long long* p, long long v) {

@@ -213,6 +213,20 @@ __device__ __forceinline__ float4 unpack_bf16x4(uint2 q) {
 #ifndef DAMD_BWD_SPLIT
 #define DAMD_BWD_SPLIT 1
 #endif
+//   FIXW    the fixed-point decodes of the flagship kernels (bwd: the four dense-1 sums a thread
+//           turns into h; fwd: the pending conv gradient): 0 from_fix, 1 from_fix_wave -- the
+//           narrow form when a wave-uniform test finds every value inside it, from_fix otherwise
+//   CGPRE   the conv gradient: 0 conv_grad, which decodes each argmax code where it uses it; 1 the
+//           staging waves translate the codes into pre-decoded entries (code_entries) and the
+//           gradient reads entries, dP values and x taps in two LDS batches, addresses from
+//           per-thread bases and immediate offsets.  Same products, same order of additions.
+// The generic kernels keep 0 / 0: flagship against generic compares the new code with the old.
+#ifndef DAMD_FIXW
+#define DAMD_FIXW 1
+#endif
+#ifndef DAMD_BWD_CGPRE
+#define DAMD_BWD_CGPRE 1
+#endif
 // The bf16 copy of W1 is double-buffered by step parity: in a step of parity p every reader
 // (fwd's dense-1 operand, bwd's dP operand) reads buffer p, and the eager update in bwd writes
 // buffer p ^ 1, which the next step (parity p ^ 1) reads; the deferred update in fwd writes
@@ -228,18 +242,20 @@ struct CfgGeneric {
   static constexpr int NT = 512, BAL = 0, STORES = 0;
   static constexpr bool D1REG = false;
   static constexpr int AUX = 0, SPLIT = 0;
+  static constexpr bool FIXW = false, CGPRE = false;
 };
 struct CfgFlagFwd {
   static constexpr int PP = 3, LG = 4;
   static constexpr bool B64 = true, EAGER = true, SH = false;
   static constexpr int BAL = DAMD_FWD_BAL, STORES = DAMD_FWD_STORES, NT = BAL == 1 ? 768 : 512;
-  static constexpr bool D1REG = DAMD_FWD_D1REG != 0;
+  static constexpr bool D1REG = DAMD_FWD_D1REG != 0, FIXW = DAMD_FIXW != 0;
   static_assert(BAL >= 0 && BAL <= 2 && STORES >= 0 && STORES <= 2, "fwd wave mapping");
 };
 struct CfgFlagBwd {
   static constexpr int PP = 2, LG = 0;
   static constexpr bool B64 = true, EAGER = true, SH = false;
   static constexpr int NT = DAMD_BWD_NT, AUX = DAMD_BWD_AUX, SPLIT = DAMD_BWD_SPLIT;
+  static constexpr bool FIXW = DAMD_FIXW != 0, CGPRE = DAMD_BWD_CGPRE != 0 && NT == 1024;  // (CGPRE builds on 16 waves)
   static_assert((NT == 512 || NT == 1024) && AUX >= 0 && AUX <= 1 && SPLIT >= 0 && SPLIT <= 1, "bwd wave mapping");
   // blocks of the grid
   static constexpr int NSC = (convnet::NPOS + PP - 1) / PP, GRID = SPLIT ? 2 * NSC : NSC;
@@ -486,8 +502,12 @@ __device__ __forceinline__ void fwd_body(const void* __restrict__ xnext, uint16_
   };
   if (!sh) w1_update();
   float cwn = 0.f, cvn = 0.f;
-  if (tid < NCONV) {
-    sgd_or_keep(pend, cp, from_fix(cq, CINV), cv, c, cwn, cvn);
+  if (tid < NCONV) {  // (5 whole waves)
+    float cg[1];
+    const long long cqa[1] = {cq};
+    if constexpr (C::FIXW) from_fix_wave(cg, cqa, CINV);
+    else cg[0] = from_fix(cq, CINV);
+    sgd_or_keep(pend, cp, cg[0], cv, c, cwn, cvn);
     // weights: split once here and stored in MFMA operand order, not per wave and lane
     if (tid < OFF_BC) conv_w_store(wf, wfs, cwn);
     else cb[tid - OFF_BC] = cwn;
@@ -827,6 +847,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   constexpr int cprobe = DAMD_PROBE_HCONV;  // 0 in every product build (see the top of the file)
   Stamps sts;
   unsigned long long wst_dh = 0, wst_cg = 0;  // this wave's arrival at two barriers (slots 14 / 15)
+  unsigned long long wst_red = 0;             // and at the barrier ahead of the `red` reduction (extra rows)
   stamp(sts, st, 0);
   constexpr int NSC = SPEC ? (NPOS + C::PP - 1) / C::PP : 1;  // (constant configuration: the slices)
   // a role per block (CfgFlagBwd::SPLIT; blockIdx.x is scalar, so every role branch is a scalar
@@ -848,6 +869,10 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   constexpr int NT = C::NT, NW = NT / 64;
   constexpr bool W16 = NT == 1024, AUXD = C::AUX != 0;
   static_assert(SPEC || (NT == 512 && !AUXD), "the generic kernels keep the plain mapping");
+  // CGP: the code tile holds the conv gradient's pre-decoded entries (CfgFlagBwd::CGPRE), two bytes per code
+  constexpr bool CGP = SPEC && C::CGPRE;
+  static_assert(!CGP || W16, "the pre-decoded conv gradient builds on the 16-wave mapping");
+  const int CSB = CH * KC * (CGP ? CGE_BYTES : 1);
   // (AUXD: dps behind the head scratch in a region of its own, so the head scratch stays
   // readable to the end of the kernel; convnet2_bwd_lds sizes the flagship's LDS for it)
   const int RB = AUXD ? HEAD_BYTES + CH * KD * 4 : max(CH * KD * 4, HEAD_BYTES);
@@ -864,14 +889,14 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   const int o_dps = SPLIT ? HEAD_BYTES + XS_BYTES : XS_BYTES + (AUXD ? HEAD_BYTES : 0);
   const int o_pt = SPLIT ? HEAD_BYTES : XS_BYTES + RB, o_dht = o_pt + PTB;
   const int o_dhs = SPLIT ? o_dps + DPSB : o_dht + DHTB, o_w1s = o_dhs + DHSB, o_cs = o_w1s + PTB;
-  const int o_red = SPLIT ? o_cs + CH * KC : o_pt, o_ared = SPLIT ? o_dht + DHTB : o_dps;
+  const int o_red = SPLIT ? o_cs + CSB : o_pt, o_ared = SPLIT ? o_dht + DHTB : o_dps;
   float* xs = reinterpret_cast<float*>(smem + o_xs);                       // [CH][XR][28]
   float* dps = reinterpret_cast<float*>(smem + o_dps);                     // [CH][KD] (after the head)
   uint16_t* pt = reinterpret_cast<uint16_t*>(smem + o_pt);                 // [PP*32][HP]
   uint16_t* dht = reinterpret_cast<uint16_t*>(smem + o_dht);               // [2][HID][HP] dh^T hi, lo
   uint16_t* dhs = reinterpret_cast<uint16_t*>(smem + o_dhs);               // [2][CH][HP]  dh hi, lo
   uint16_t* w1s = reinterpret_cast<uint16_t*>(smem + o_w1s);               // [PP*32][HP]
-  uint8_t* cs = reinterpret_cast<uint8_t*>(smem + o_cs);                   // [CH][KC] argmax codes
+  uint8_t* cs = reinterpret_cast<uint8_t*>(smem + o_cs);                   // [CH][KC] argmax codes (CGP: entries)
   float* red = reinterpret_cast<float*>(smem + o_red);  // [16][320] reduction scratch, after the MFMAs
   // head scratch (aliases dps unless AUXD: used before the dP MFMA of each chunk)
   float* hs = reinterpret_cast<float*>(smem + o_head);  // [CH][HPITCH] h = relu(dense-1)
@@ -1088,6 +1113,21 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
     if (i < (SPEC ? PP * 32 * 8 : K * 8)) *reinterpret_cast<uint4*>(pt + (i >> 3) * HP + (i & 7) * 8) = v;
   };
   auto store_cv = [&](const uint4& v, bool ok, int i) __attribute__((always_inline)) {
+    if constexpr (CGP) {
+      // 16 codes -> 16 entries (code_entries); a unit that was not loaded -- the short last
+      // slice's positions >= NPOS -- as code 0: off, offset 0
+      const int bb = i / KCM, q = i - bb * KCM;
+      const uint32_t w[4] = {ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u};
+      uint32_t e[8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) code_entries(w[k], e[2 * k], e[2 * k + 1]);
+      if (i < CH * KCM) {
+        uint4* dst = reinterpret_cast<uint4*>(cs + (bb * KC + q * 16) * CGE_BYTES);
+        dst[0] = make_uint4(e[0], e[1], e[2], e[3]);
+        dst[1] = make_uint4(e[4], e[5], e[6], e[7]);
+      }
+      return;
+    }
     if constexpr (SPEC) {
       const int bb = i / KCM, q = i - bb * KCM;
       if (i < CH * KCM) *reinterpret_cast<uint4*>(cs + bb * KC + q * 16) = ok ? v : make_uint4(0u, 0u, 0u, 0u);
@@ -1226,13 +1266,24 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
       const int r = tid >> HQS, q = tid & ((1 << HQS) - 1);
       const bool rv = chunk * CH + r < B;
       const uint4 hq[4] = {hq0, hq1, hq2, hq3};
+      long long hq64[2 * HQN];
+      float hf[2 * HQN];
 #pragma unroll
       for (int u = 0; u < HQN; ++u) {
-        const long long a = (long long)(((unsigned long long)hq[u].y << 32) | hq[u].x);
-        const long long b = (long long)(((unsigned long long)hq[u].w << 32) | hq[u].z);
-        const int n = q * 2 * HQN + 2 * u;
-        hs[r * HPITCH + n] = rv ? fmaxf(from_fix(a, HINV) + spl[n], 0.f) : 0.f;
-        hs[r * HPITCH + n + 1] = rv ? fmaxf(from_fix(b, HINV) + spl[n + 1], 0.f) : 0.f;
+        hq64[2 * u] = (long long)(((unsigned long long)hq[u].y << 32) | hq[u].x);
+        hq64[2 * u + 1] = (long long)(((unsigned long long)hq[u].w << 32) | hq[u].z);
+      }
+      // (every thread of the block is here: the wave-uniform test sees whole waves)
+      if constexpr (C::FIXW) {
+        from_fix_wave(hf, hq64, HINV);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 2 * HQN; ++i) hf[i] = from_fix(hq64[i], HINV);
+      }
+#pragma unroll
+      for (int i = 0; i < 2 * HQN; ++i) {
+        const int n = q * 2 * HQN + i;
+        hs[r * HPITCH + n] = rv ? fmaxf(hf[i] + spl[n], 0.f) : 0.f;
       }
     }
     lds_barrier();
@@ -1448,8 +1499,59 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
         }
       }
     };
+    // The same sums from the pre-decoded entries (CGP, see code_entries): conv_grad spends most
+    // of its VALU stream on decoding and address arithmetic, per pair and behind a full LDS wait
+    // each, and the phase is VALU-issue bound.  Here a pair costs an address add and the mask
+    // `and`: the entry's offset byte is added to a per-thread base (image group and position
+    // folded in, the position's (py, px) part scalar), image and tap steps are immediate
+    // offsets; the loads come in two batches -- every entry and dP value, then every x tap --
+    // and the fmaf chains run in conv_grad's order (image outer, position inner, taps ascending).
+    // Positions >= NPOS of the short last slice are not skipped: their entries are `off` (d = +0,
+    // as for any unit that was off), their base is the slice's last real position, so every x read
+    // is of staged, finite rows and fmaf(+0, x, g) leaves g (never -0) as it is.
+    auto conv_grad_pre = [&](auto t0c, auto t1c) __attribute__((always_inline)) {
+      constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NPL = SPEC ? C::PP : 1;
+      const uint8_t* ce = cs + (grp * 4 * KC + ch) * CGE_BYTES;
+      const float* dp = dps + grp * 4 * KD + ch;
+      uint32_t eo[4][NPL];
+      int em[4][NPL];
+      float dv[4][NPL];
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+          eo[ii][pl] = ce[(ii * KC + pl * 32) * CGE_BYTES];
+          em[ii][pl] = reinterpret_cast<const int8_t*>(ce)[(ii * KC + pl * 32) * CGE_BYTES + 1];
+          dv[ii][pl] = dp[ii * KD + pl * 32];
+        }
+      const char* xg = reinterpret_cast<const char*>(xs) + grp * (4 * XR * IMG * 4);
+      float xv[4][NPL][T1 - T0];
+#pragma unroll
+      for (int pl = 0; pl < NPL; ++pl) {
+        const int pos = min(p0 + pl, NPOS - 1), py = pos / PO, px = pos - py * PO;
+        const char* xb = xg + ((2 * py - r0) * IMG + 2 * px) * 4;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+          const float* xp = reinterpret_cast<const float*>(xb + eo[ii][pl]);
+#pragma unroll
+          for (int t = T0; t < T1; ++t) xv[ii][pl][t - T0] = xp[ii * XR * IMG + (t / 3) * IMG + (t % 3)];
+        }
+      }
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+          const float d = __int_as_float(__float_as_int(dv[ii][pl]) & em[ii][pl]);
+#pragma unroll
+          for (int t = T0; t < T1; ++t) gw[t] = fmaf(d, xv[ii][pl][t - T0], gw[t]);
+          if (T1 == 9) gb += d;
+        }
+    };
     using std::integral_constant;
-    if (!W16) conv_grad(integral_constant<int, 0>{}, integral_constant<int, 9>{});
+    if constexpr (CGP) {
+      if (half == 0) conv_grad_pre(integral_constant<int, 0>{}, integral_constant<int, 5>{});
+      else conv_grad_pre(integral_constant<int, 5>{}, integral_constant<int, 9>{});
+    } else if (!W16) conv_grad(integral_constant<int, 0>{}, integral_constant<int, 9>{});
     else if (half == 0) conv_grad(integral_constant<int, 0>{}, integral_constant<int, 5>{});
     else conv_grad(integral_constant<int, 5>{}, integral_constant<int, 9>{});
   }
@@ -1479,6 +1581,7 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   }
   float* ared = reinterpret_cast<float*>(smem + o_ared);
   if (rw1 && (!W16 || tid < 512)) ared[tid] = arsum;  // (aux_split maps 512 threads)
+  if (st != nullptr) wst_red = __builtin_amdgcn_s_memrealtime();  // (conv gradient done, its sums stored)
   lds_barrier();
   // this slice's conv-gradient partial, fixed order over the 16 thread groups, then a
   // 64-bit fixed-point atomic add (order-independent sum over the slices)
@@ -1527,6 +1630,14 @@ __device__ __forceinline__ void bwd_body(long long* __restrict__ hacc, const int
   if (st != nullptr && tid == 64 * (s % NW)) {
     st[blockIdx.x * 16 + 14] = (wst_dh & 0x00ffffffffffffffull) | ((unsigned long long)(s % NW) << 56);
     st[blockIdx.x * 16 + 15] = (wst_cg & 0x00ffffffffffffffull) | ((unsigned long long)NW << 56);
+    // the same wave's arrival at the barrier ahead of the `red` reduction -- the end of its conv
+    // gradient (wave 0's slot 4 is stamped when wave 0 gets there, and what it then waits for is
+    // the slowest wave).  The 16 slots of a block's row are taken: block b's value goes to slot
+    // b & 15 of row nblk + (b >> 4), behind the nblk rows of the grid (<= 170 blocks of 256 rows;
+    // nblk a constant in the flagship kernel: gridDim would pull in the hidden kernel arguments)
+    const int nblk = SPEC ? (SPLIT ? 2 * NSC : NSC) : (int)gridDim.x;
+    st[(nblk + ((int)blockIdx.x >> 4)) * 16 + ((int)blockIdx.x & 15)] =
+        (wst_red & 0x00ffffffffffffffull) | ((unsigned long long)(s % NW) << 56);
   }
 }
 
@@ -1721,13 +1832,17 @@ size_t convnet2_fwd_lds(int PP, int lg) {
 // scratch instead of aliasing it)
 // LDS bytes one role of the flagship backward needs (CfgFlagBwd::SPLIT; role 0 conv, 1 W1):
 // the layouts of bwd_body
-//   conv role  head | xs | dps | dhs | w1s | cs | red
+//   conv role  head | xs | dps | dhs | w1s | cs | red   (cs: a byte per code, or the conv
+//              gradient's pre-decoded entries, CfgFlagBwd::CGPRE)
 //   W1 role    head | pt | dht | ared (one float per aux thread)
+static size_t bwd_flag_code_bytes(int PP) {
+  return (size_t)convnet::CH * PP * 32 * (convnet2::CfgFlagBwd::CGPRE ? convnet::CGE_BYTES : 1);
+}
 size_t convnet2_bwd_role_lds(int PP, int role) {
   using namespace convnet;
   const size_t head = (size_t)convnet2::HEAD_BYTES, tile = (size_t)PP * 32 * HP * 2, slack = 16 + 256 * 4;
   if (role == 0)
-    return head + XS_BYTES + (size_t)CH * (PP * 32 + 4) * 4 + (size_t)2 * CH * HP * 2 + tile + (size_t)CH * PP * 32 +
+    return head + XS_BYTES + (size_t)CH * (PP * 32 + 4) * 4 + (size_t)2 * CH * HP * 2 + tile + bwd_flag_code_bytes(PP) +
            (size_t)16 * NCONV * 4 + slack;
   return head + tile + (size_t)2 * HID * HP * 2 + (size_t)512 * 4 + slack;
 }
@@ -1748,7 +1863,7 @@ size_t convnet2_bwd_lds(int PP, bool flagship) {
   const size_t redb = (size_t)16 * NCONV * 4;  // `red` spans pt + dht after the MFMAs
   const size_t ptdht = (size_t)PP * 32 * HP * 2 + (size_t)2 * HID * HP * 2;
   return XS_BYTES + rb + (ptdht > redb ? ptdht : redb) + (size_t)2 * CH * HP * 2 + (size_t)PP * 32 * HP * 2 +
-         (size_t)CH * PP * 32 + 16 + 256 * 4;
+         (flagship ? bwd_flag_code_bytes(PP) : (size_t)CH * PP * 32) + 16 + 256 * 4;
 }
 
 // eager W1 update: world-1 runs with the single-chunk backward (B <= 64) only

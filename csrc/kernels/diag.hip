@@ -4,6 +4,8 @@
 // concurrently (e.g. a gradient all-reduce node beside the backward kernels).
 #include <hip/hip_runtime.h>
 
+#include "convnet_dev.h"
+
 namespace damd {
 namespace {
 
@@ -42,6 +44,27 @@ __global__ __launch_bounds__(1024) void lds_count_k(unsigned long long* __restri
   if (n) __hip_atomic_fetch_add(out, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Test-only (tests/test_fixpoint_decode_gpu.py): the step kernels' two fixed-point decodes on the
+// same inputs -- from_fix_wave as the backward's h phase calls it (4 consecutive values per
+// thread, one wave-uniform test per wave) into `fast`, from_fix into `ref`.  n: a multiple of 4.
+template <int SCALE>  // 0: HINV (dense-1 sums), 1: CINV (conv gradient)
+__global__ __launch_bounds__(256) void fix_decode_k(const long long* __restrict__ q, float* __restrict__ fast,
+                                                    float* __restrict__ ref, int n) {
+  constexpr double inv = SCALE == 0 ? convnet::HINV : convnet::CINV;
+  const int i = 4 * (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  long long v[4];
+  float f[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = q[i + j];
+  convnet::from_fix_wave(f, v, inv);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    fast[i + j] = f[j];
+    ref[i + j] = convnet::from_fix(v[j], inv);
+  }
+}
+
 hipError_t lds_all(const void* k) {
   return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
 }
@@ -62,6 +85,16 @@ hipError_t lds_count(int blocks, unsigned long long* out, hipStream_t s) {
   const hipError_t e = lds_all((const void*)lds_count_k);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(lds_count_k, dim3(blocks), dim3(1024), LDS_ALL, s, out);
+  return hipGetLastError();
+}
+
+// fast[i] = from_fix_wave, ref[i] = from_fix of q[i], i < n (n a multiple of 4); scale 0: 2^-32, 1: 2^-40
+hipError_t fix_decode(const long long* q, float* fast, float* ref, int n, int scale, hipStream_t s) {
+  if (q == nullptr || fast == nullptr || ref == nullptr || n < 4 || n % 4 != 0 || scale < 0 || scale > 1)
+    return hipErrorInvalidValue;
+  const dim3 grid((n / 4 + 255) / 256);
+  if (scale == 0) hipLaunchKernelGGL(fix_decode_k<0>, grid, dim3(256), 0, s, q, fast, ref, n);
+  else hipLaunchKernelGGL(fix_decode_k<1>, grid, dim3(256), 0, s, q, fast, ref, n);
   return hipGetLastError();
 }
 

@@ -34,6 +34,7 @@ namespace damd {
 hipError_t spin_stamp(long long ticks, int blocks, unsigned long long* out, int slot, hipStream_t s);
 hipError_t lds_poison(int blocks, hipStream_t s);
 hipError_t lds_count(int blocks, unsigned long long* out, hipStream_t s);
+hipError_t fix_decode(const long long* q, float* fast, float* ref, int n, int scale, hipStream_t s);
 }
 
 void register_kernel_ops(py::module_& m) {
@@ -48,6 +49,11 @@ void register_kernel_ops(py::module_& m) {
   });
   m.def("lds_count", [](int blocks, uintptr_t out, uintptr_t s) {
     check(damd::lds_count(blocks, P_<unsigned long long>(out), P_<ihipStream_t>(s)), "lds_count");
+  });
+  // tests only: the step kernels' fixed-point decode, wave-uniform fast path against from_fix
+  m.def("fix_decode", [](uintptr_t q, uintptr_t fast, uintptr_t ref, int n, int scale, uintptr_t s) {
+    check(damd::fix_decode(P_<const long long>(q), P_<float>(fast), P_<float>(ref), n, scale, P_<ihipStream_t>(s)),
+          "fix_decode");
   });
   m.def(
       "gemm",

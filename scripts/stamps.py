@@ -72,14 +72,20 @@ def main():
         if kn == "fwd":
             per_wave(a)
         elif kn != "bwd W1 role":  # (slot 15 is the conv role's pre-conv-gradient barrier)
-            per_wave_bwd(a)
+            # the recorded wave's arrival at the barrier ahead of the `red` reduction: block b's
+            # value is slot b & 15 of row nblk + (b >> 4), behind the rows of the grid
+            red = st[k, nblk:].astype(np.int64).reshape(-1)[lo:hi]
+            per_wave_bwd(a, red)
 
 
-def per_wave_bwd(a):
+def per_wave_bwd(a, red):
     """bwd slots 14 / 15: block s records the view of wave s mod NW -- its arrival at the dh
     barrier and at the pre-conv-gradient barrier (wave 0 records the time it LEAVES them in
     slots 8 and 3).  The top byte of slot 14 is the wave, of slot 15 the waves per block.
-    Medians over the blocks that recorded the wave, in us since the block's own start."""
+    red: per block, the same wave's arrival at the barrier ahead of the `red` reduction, i.e. the
+    end of its conv gradient (wave 0's own arrival is slot 4, 'convgrad').
+    Medians over the blocks that recorded the wave, in us since the block's own start; then the
+    conv gradient's span: pre-conv-gradient barrier left (slot 3) to the last recorded arrival."""
     mask = (1 << 56) - 1
     ok = (a[:, 15] != 0) & (a[:, 0] > 0)
     if not ok.any():
@@ -88,15 +94,28 @@ def per_wave_bwd(a):
     wave = a[:, 14] >> 56
     print(f"bwd per wave ({nw} waves per block; median us since the block's own start of the wave's ARRIVAL at the barrier;")
     print("   '0 leaves': when wave 0 leaves it, i.e. after the last arrival)")
-    print("   wave  blocks  dh barrier  pre-conv-grad barrier")
+    print("   wave  blocks  dh barrier  pre-conv-grad barrier  red barrier  conv gradient (from slot 3)")
     rows = a[ok]
     print(f"   0 leaves {len(rows):3d}  {statistics.median((rows[:, 8] - rows[:, 0]) / 100.0):10.2f}  "
           f"{statistics.median((rows[:, 3] - rows[:, 0]) / 100.0):21.2f}")
+    has_red = ok & ((red & mask) > 0)
+    span = {}
     for w in range(nw):
-        rows = a[ok & (wave == w)]
+        sel = ok & (wave == w)
+        rows = a[sel]
         if len(rows):
             d = [statistics.median(((rows[:, s] & mask) - rows[:, 0]) / 100.0) for s in (14, 15)]
-            print(f"   {w:4d}  {len(rows):6d}  {d[0]:10.2f}  {d[1]:21.2f}")
+            line = f"   {w:4d}  {len(rows):6d}  {d[0]:10.2f}  {d[1]:21.2f}"
+            rsel = sel & has_red
+            if rsel.any():
+                r = red[rsel] & mask
+                span[w] = statistics.median((r - a[rsel][:, 3]) / 100.0)
+                line += f"  {statistics.median((r - a[rsel][:, 0]) / 100.0):11.2f}  {span[w]:13.2f}"
+            print(line)
+    if span:
+        w0 = a[has_red]
+        print(f"   conv gradient: wave 0 alone (slot 4 - slot 3) median {statistics.median((w0[:, 4] - w0[:, 3]) / 100.0):.2f} us; "
+              f"to the last wave's arrival (largest per-wave median, wave {max(span, key=span.get)}) {max(span.values()):.2f} us")
 
 
 def per_wave(a):
