@@ -159,18 +159,20 @@ compile <- function(object, optimizer = NULL, loss = NULL, metrics = NULL, ...) 
 #' @export
 fit <- function(object, x = NULL, y = NULL, batch_size = NULL, epochs = 10, verbose = 1, callbacks = NULL,
                 steps_per_epoch = NULL, validation_split = 0, validation_data = NULL, shuffle = TRUE,
-                initial_epoch = 0, ...) {
+                initial_epoch = 0, class_weight = NULL, sample_weight = NULL, ...) {
+  # class_weight: a named list, list("0" = 1, "1" = 2.5); the names become the integer class ids
   h <- .r()$fit(object, x = x, y = y, batch_size = .int(batch_size), epochs = .int(epochs), verbose = .int(verbose),
                 callbacks = callbacks, steps_per_epoch = .int(steps_per_epoch), validation_split = validation_split,
-                validation_data = validation_data, shuffle = shuffle, initial_epoch = .int(initial_epoch), ...)
+                validation_data = validation_data, shuffle = shuffle, initial_epoch = .int(initial_epoch),
+                class_weight = class_weight, sample_weight = sample_weight, ...)
   structure(list(params = reticulate::py_to_r(h$params),
                  metrics = lapply(reticulate::py_to_r(h$history), unlist),
                  py = h), class = "keras_training_history")
 }
 
 #' @export
-evaluate <- function(object, x, y, batch_size = NULL, verbose = 1) {
-  .r()$evaluate(object, x, y, batch_size = .int(batch_size), verbose = .int(verbose))
+evaluate <- function(object, x, y, batch_size = NULL, verbose = 1, sample_weight = NULL) {
+  .r()$evaluate(object, x, y, batch_size = .int(batch_size), verbose = .int(verbose), sample_weight = sample_weight)
 }
 
 #' @export

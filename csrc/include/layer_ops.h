@@ -161,18 +161,24 @@ hipError_t colsum(const void* x, int x_f32, int M, int N, int ld, float* out, fl
 // kernel re-arms it): the batch sums are formed in a fixed order, not by float atomics.
 // bias_grad (optional): += the column sums of the stored dlogits, exactly as colsum with one
 // split (the logits layer's bias gradient without a colsum launch)
+// weights (optional, fp32): row b's gradient and loss are multiplied by its weight, the correct
+// and valid counts are not.  ctrl == nullptr: weights[b]; else the weight of the sample at the
+// device cursor, weights[cursor * global_batch + row0 + b] (modulo nsamples in wrap mode).  A
+// row with label < 0 does not read the array.  nullptr launches the unweighted kernel.
 hipError_t softmax_xent(const float* logits, int ld, const int32_t* labels, int B, int K, float scale,
                         const Ctrl* ctrl, uint16_t* dlogits, float* tail, float* rows, hipStream_t s,
-                        float* bias_grad = nullptr);
+                        float* bias_grad = nullptr, const float* weights = nullptr);
 // The same against dense fp32 target rows [.][K] (one-hot or soft; label_smoothing eps in
 // [0, 1): y' = y (1 - eps) + eps / K): loss = -sum y' log softmax, dlogits = (softmax *
 // sum y' - y') * scale, correct = argmax logits == argmax y (first max wins on both).
 // ctrl != nullptr: block b reads target row cursor * global_batch + row0 + b (modulo
 // nsamples in wrap mode) of the epoch-ordered targets and labels[b] < 0 masks the row;
-// ctrl == nullptr: target row b, labels optional.  tail / rows / bias_grad as softmax_xent.
+// ctrl == nullptr: target row b, labels optional.  tail / rows / bias_grad as softmax_xent;
+// weights are indexed by the target row.
 hipError_t softmax_xent_dense(const float* logits, int ld, const int32_t* labels, const float* targets, int B, int K,
                               float label_smoothing, float scale, const Ctrl* ctrl, uint16_t* dlogits, float* tail,
-                              float* rows, hipStream_t s, float* bias_grad = nullptr);
+                              float* rows, hipStream_t s, float* bias_grad = nullptr,
+                              const float* weights = nullptr);
 
 // Optimizer ---------------------------------------------------------------------------------
 // flat multi-tensor Keras SGD over the master buffer: P, V fp32 updated from G; Pb = bf16(P)

@@ -139,10 +139,20 @@ __device__ __forceinline__ void sx_tail(float row_loss, float row_corr, float ro
   }
 }
 
+// W: a per-row weight (Keras sample / class weights) multiplies the row's gradient and loss,
+// not its correct / valid counts: weights[b] without ctrl, else the weight of the sample at
+// the device cursor, weights[cursor * global_batch + row0 + b] (modulo nsamples in wrap
+// mode) -- the row softmax_xent_dense_k reads its targets from.  A row with label < 0 does
+// not read the array.  The weights pointer is an argument of the W = true instantiation
+// alone (Wt = const float*): W = false (no Wt) keeps the argument list, the kernarg layout
+// and the instruction stream of the unweighted kernel as it was before there were weights.
+__device__ __forceinline__ const float* sx_weights() { return nullptr; }
+__device__ __forceinline__ const float* sx_weights(const float* w) { return w; }
+template <bool W, typename... Wt>
 __global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ logits, int ld,
                                                      const int32_t* __restrict__ labels, int K, float scale,
                                                      const Ctrl* __restrict__ ctrl, uint16_t* __restrict__ dl,
-                                                     float* tail, float* rows, float* bias_grad) {
+                                                     float* tail, float* rows, float* bias_grad, Wt... weights) {
   __shared__ float wmax[SX_NW], wsum[SX_NW];
   __shared__ int widx[SX_NW];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -151,10 +161,20 @@ __global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ l
   if (y < 0) {
     for (int k = t; k < K; k += NT) dl[(size_t)b * ld + k] = 0;
   } else {
+    [[maybe_unused]] long row = b;
     if (ctrl) {
       const int gb = ctrl->global_batch;
       const int left = ctrl->nsamples - ctrl->cursor * gb;
       scale = 1.f / (float)(ctrl->wrap > 0 ? gb : max(1, min(gb, left)));
+      if constexpr (W) {
+        const long base = (long)ctrl->cursor * gb + ctrl->row0;
+        row = ctrl->wrap > 0 ? (base + b) % ctrl->nsamples : base + b;
+      }
+    }
+    [[maybe_unused]] float wt = 1.f;
+    if constexpr (W) {
+      wt = sx_weights(weights...)[row];
+      scale *= wt;
     }
     const float* z = logits + (size_t)b * ld;
     const bool reg = K <= SX_KPT * NT;  // the row fits the registers
@@ -211,10 +231,14 @@ __global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ l
       }
     }
     row_loss = logf(sum) + zmax - z[y];
+    if constexpr (W) row_loss *= wt;
     row_corr = amax == y ? 1.f : 0.f;
   }
   sx_tail(row_loss, row_corr, y < 0 ? 0.f : 1.f, K, ld, dl, tail, rows, bias_grad);
 }
+template __global__ void softmax_xent_k<false>(const float* __restrict__, int, const int32_t* __restrict__, int, float,
+                                               const Ctrl* __restrict__, uint16_t* __restrict__, float*, float*,
+                                               float*);
 
 // Softmax cross-entropy against dense fp32 target rows (one-hot / soft targets) with label
 // smoothing: y' = y (1 - eps) + eps / K, S = sum y', loss = S lse - sum y' z, dlogits =
@@ -225,12 +249,15 @@ __global__ __launch_bounds__(NT) void softmax_xent_k(const float* __restrict__ l
 // With ctrl the block finds its target row as gather_batch_k finds the input row (the
 // epoch-ordered [n][K] targets are read in place), else targets are indexed by the block.
 // labels (optional): labels[b] < 0 marks a row past the end of the data.
+// W: weights[row] of that same row multiplies the gradient and the loss (softmax_xent_k,
+// instantiated the same way).
+template <bool W, typename... Wt>
 __global__ __launch_bounds__(NT) void softmax_xent_dense_k(const float* __restrict__ logits, int ld,
                                                            const int32_t* __restrict__ labels,
                                                            const float* __restrict__ targets, int K, float eps,
                                                            float scale, const Ctrl* __restrict__ ctrl,
                                                            uint16_t* __restrict__ dl, float* tail, float* rows,
-                                                           float* bias_grad) {
+                                                           float* bias_grad, Wt... weights) {
   __shared__ float wmax[SX_NW], wymax[SX_NW], wS[SX_NW], wdot[SX_NW], wsum[SX_NW];
   __shared__ int widx[SX_NW], wyidx[SX_NW];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -246,6 +273,11 @@ __global__ __launch_bounds__(NT) void softmax_xent_dense_k(const float* __restri
       scale = 1.f / (float)(ctrl->wrap > 0 ? gb : max(1, min(gb, left)));
       const long base = (long)ctrl->cursor * gb + ctrl->row0;
       row = ctrl->wrap > 0 ? (base + b) % ctrl->nsamples : base + b;
+    }
+    [[maybe_unused]] float wt = 1.f;
+    if constexpr (W) {
+      wt = sx_weights(weights...)[row];
+      scale *= wt;
     }
     const float* z = logits + (size_t)b * ld;
     const float* yt = targets + (size_t)row * K;
@@ -336,10 +368,15 @@ __global__ __launch_bounds__(NT) void softmax_xent_dense_k(const float* __restri
       }
     }
     row_loss = S * (logf(sum) + zmax) - dot;
+    if constexpr (W) row_loss *= wt;
     row_corr = amax == ymaxi ? 1.f : 0.f;
   }
   sx_tail(row_loss, row_corr, valid ? 1.f : 0.f, K, ld, dl, tail, rows, bias_grad);
 }
+template __global__ void softmax_xent_dense_k<false>(const float* __restrict__, int, const int32_t* __restrict__,
+                                                     const float* __restrict__, int, float, float,
+                                                     const Ctrl* __restrict__, uint16_t* __restrict__, float*, float*,
+                                                     float*);
 
 // ---- inference outputs ---------------------------------------------------------------------
 // logits rows of this step -> out[global row][K] (rows past the end of the data dropped);
@@ -410,6 +447,17 @@ __global__ __launch_bounds__(NT) void softmax_store_k(const float* __restrict__ 
   }
 }
 
+// ---- the weighted loss kernels ---------------------------------------------------------------
+template __global__ void softmax_xent_k<true, const float*>(const float* __restrict__, int,
+                                                            const int32_t* __restrict__, int, float,
+                                                            const Ctrl* __restrict__, uint16_t* __restrict__, float*,
+                                                            float*, float*, const float*);
+template __global__ void softmax_xent_dense_k<true, const float*>(const float* __restrict__, int,
+                                                                  const int32_t* __restrict__,
+                                                                  const float* __restrict__, int, float, float,
+                                                                  const Ctrl* __restrict__, uint16_t* __restrict__,
+                                                                  float*, float*, float*, const float*);
+
 }  // namespace
 
 int colsum_splits(int M, int N) {
@@ -427,23 +475,32 @@ hipError_t colsum(const void* x, int x_f32, int M, int N, int ld, float* out, fl
 }
 
 hipError_t softmax_xent(const float* logits, int ld, const int32_t* labels, int B, int K, float scale, const Ctrl* ctrl,
-                        uint16_t* dlogits, float* tail, float* rows, hipStream_t s, float* bias_grad) {
+                        uint16_t* dlogits, float* tail, float* rows, hipStream_t s, float* bias_grad,
+                        const float* weights) {
   if (!rows || B < 1) return hipErrorInvalidValue;
   if (bias_grad && colsum_splits(B, K) != 1) return hipErrorInvalidValue;  // the fold keeps colsum's order
-  hipLaunchKernelGGL(softmax_xent_k, dim3(B), dim3(NT), 0, s, logits, ld, labels, K, scale, ctrl, dlogits, tail, rows,
-                     bias_grad);
+  if (weights)
+    hipLaunchKernelGGL((softmax_xent_k<true, const float*>), dim3(B), dim3(NT), 0, s, logits, ld, labels, K, scale,
+                       ctrl, dlogits, tail, rows, bias_grad, weights);
+  else
+    hipLaunchKernelGGL(softmax_xent_k<false>, dim3(B), dim3(NT), 0, s, logits, ld, labels, K, scale, ctrl, dlogits,
+                       tail, rows, bias_grad);
   return hipGetLastError();
 }
 
 hipError_t softmax_xent_dense(const float* logits, int ld, const int32_t* labels, const float* targets, int B, int K,
                               float label_smoothing, float scale, const Ctrl* ctrl, uint16_t* dlogits, float* tail,
-                              float* rows, hipStream_t s, float* bias_grad) {
+                              float* rows, hipStream_t s, float* bias_grad, const float* weights) {
   if (!rows || !targets || B < 1 || K < 1 || K > ld) return hipErrorInvalidValue;
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return hipErrorInvalidValue;
   if (ctrl && !labels) return hipErrorInvalidValue;  // the step's row validity comes from gather_batch
   if (bias_grad && colsum_splits(B, K) != 1) return hipErrorInvalidValue;  // the fold keeps colsum's order
-  hipLaunchKernelGGL(softmax_xent_dense_k, dim3(B), dim3(NT), 0, s, logits, ld, labels, targets, K, label_smoothing,
-                     scale, ctrl, dlogits, tail, rows, bias_grad);
+  if (weights)
+    hipLaunchKernelGGL((softmax_xent_dense_k<true, const float*>), dim3(B), dim3(NT), 0, s, logits, ld, labels,
+                       targets, K, label_smoothing, scale, ctrl, dlogits, tail, rows, bias_grad, weights);
+  else
+    hipLaunchKernelGGL(softmax_xent_dense_k<false>, dim3(B), dim3(NT), 0, s, logits, ld, labels, targets, K,
+                       label_smoothing, scale, ctrl, dlogits, tail, rows, bias_grad);
   return hipGetLastError();
 }
 

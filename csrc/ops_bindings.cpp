@@ -351,22 +351,25 @@ void register_kernel_ops(py::module_& m) {
           "colsum");
   });
   m.def("softmax_xent", [](U logits, int ld, U labels, int B, int K, float scale, U ctrl, U dl, U tail, U rows, U s,
-                           U bias_grad) {
+                           U bias_grad, U weights) {
     check(damd::softmax_xent(P_<const float>(logits), ld, P_<const int32_t>(labels), B, K, scale,
                              P_<const damd::Ctrl>(ctrl), P_<u16>(dl), P_<float>(tail), P_<float>(rows),
-                             P_<ihipStream_t>(s), P_<float>(bias_grad)),
+                             P_<ihipStream_t>(s), P_<float>(bias_grad), P_<const float>(weights)),
           "softmax_xent");
   }, py::arg("logits"), py::arg("ld"), py::arg("labels"), py::arg("B"), py::arg("K"), py::arg("scale"),
-     py::arg("ctrl"), py::arg("dl"), py::arg("tail"), py::arg("rows"), py::arg("s"), py::arg("bias_grad") = 0);
+     py::arg("ctrl"), py::arg("dl"), py::arg("tail"), py::arg("rows"), py::arg("s"), py::arg("bias_grad") = 0,
+     py::arg("weights") = 0);
   m.def("softmax_xent_dense", [](U logits, int ld, U labels, U targets, int B, int K, float label_smoothing,
-                                 float scale, U ctrl, U dl, U tail, U rows, U s, U bias_grad) {
+                                 float scale, U ctrl, U dl, U tail, U rows, U s, U bias_grad,
+                                 U weights) {
     check(damd::softmax_xent_dense(P_<const float>(logits), ld, P_<const int32_t>(labels), P_<const float>(targets), B,
                                    K, label_smoothing, scale, P_<const damd::Ctrl>(ctrl), P_<u16>(dl),
-                                   P_<float>(tail), P_<float>(rows), P_<ihipStream_t>(s), P_<float>(bias_grad)),
+                                   P_<float>(tail), P_<float>(rows), P_<ihipStream_t>(s), P_<float>(bias_grad),
+                                   P_<const float>(weights)),
           "softmax_xent_dense");
   }, py::arg("logits"), py::arg("ld"), py::arg("labels"), py::arg("targets"), py::arg("B"), py::arg("K"),
      py::arg("label_smoothing"), py::arg("scale"), py::arg("ctrl"), py::arg("dl"), py::arg("tail"), py::arg("rows"),
-     py::arg("s"), py::arg("bias_grad") = 0);
+     py::arg("s"), py::arg("bias_grad") = 0, py::arg("weights") = 0);
   m.def("softmax_store", [](U logits, int ld, int K, int B, U ctrl, U out, U s) {
     check(damd::softmax_store(P_<const float>(logits), ld, K, B, P_<const damd::Ctrl>(ctrl), P_<float>(out),
                               P_<ihipStream_t>(s)),

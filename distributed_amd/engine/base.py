@@ -32,7 +32,7 @@ class Engine:
             seed = strategy.communicator.broadcast_object(seed, 0)
         self.shuffle_seed = int(seed)
 
-    def bind(self, x, y):  # -> DataFeed
+    def bind(self, x, y, w=None):  # -> DataFeed (w: float32 [n] per-sample loss weights, or None)
         raise NotImplementedError
 
     def start_epoch(self, epoch: int, shuffle: bool):
@@ -110,13 +110,15 @@ class Engine:
         """A model variable was overwritten from the host (refresh derived copies)."""
 
 
-def select_engine(model, strategy, per_replica: int, global_batch: int) -> Engine:
+def select_engine(model, strategy, per_replica: int, global_batch: int, weighted: bool = False) -> Engine:
+    """``weighted``: the fit carries per-sample loss weights (sample_weight / class_weight),
+    which the fused ConvNet engine does not take; the other engines do."""
     from .generic import GenericEngine
 
     if env.get_bool("DAMD_FUSED", True):
         from .fused_convnet import FusedConvNetEngine
 
-        ok, why = FusedConvNetEngine.eligible(model, strategy)
+        ok, why = FusedConvNetEngine.eligible(model, strategy, weighted)
         if ok:
             return FusedConvNetEngine(model, strategy, per_replica, global_batch)
         dlog.debug("fused ConvNet engine not used: %s", why)

@@ -33,12 +33,21 @@ def as_u8_over_255(x: np.ndarray):
 
 class DataFeed:
     def __init__(self, x, y, device: torch.device, flatten: bool = False, label_dtype=torch.int32,
-                 allow_u8: bool = False):
+                 allow_u8: bool = False, w=None):
         x = np.asarray(x)
         y = np.asarray(y)
         if len(x) != len(y):
             raise ValueError(f"x has {len(x)} rows but y has {len(y)}")
         self.n = int(len(x))
+        # per-sample loss weights (keras/utils.py resolve_sample_weights): fp32 [n] on the
+        # device in dataset order, indexed like x and y; the host copy tells whether a later
+        # bind brings the same weights
+        self.w, self.w_host = None, None
+        if w is not None:
+            self.w_host = np.array(w, dtype=np.float32).reshape(-1)
+            if self.w_host.shape[0] != self.n:
+                raise ValueError(f"x has {self.n} rows but there are {self.w_host.shape[0]} sample weights")
+            self.w = torch.from_numpy(self.w_host).to(device)
         self.sample_shape = tuple(x.shape[1:])
         u8 = as_u8_over_255(x) if allow_u8 else None
         self.x_u8 = u8 is not None
@@ -55,6 +64,13 @@ class DataFeed:
             self.y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(device)
         self.perm = torch.arange(self.n, dtype=torch.int32, device=device)
         self.device = device
+
+    def same_weights(self, w) -> bool:
+        """``w`` (None or an array) is what this feed was built with."""
+        if w is None or self.w_host is None:
+            return w is None and self.w_host is None
+        w = np.asarray(w, dtype=np.float32).reshape(-1)
+        return w.shape == self.w_host.shape and bool(np.array_equal(w, self.w_host))
 
     def set_epoch(self, epoch: int, shuffle: bool = True, seed: int = None) -> None:
         if not shuffle:

@@ -59,7 +59,7 @@ class FusedConvNetEngine(Engine):
     name = "fused_convnet"
 
     @staticmethod
-    def eligible(model, strategy):
+    def eligible(model, strategy, weighted: bool = False):
         from ..keras import layers as L
         from ..keras import losses, optimizers
 
@@ -68,6 +68,8 @@ class FusedConvNetEngine(Engine):
         ls = [l for l in getattr(model, "layers", []) if not isinstance(l, L.InputLayer)]
         if len(ls) != 5:
             return False, "layer count"
+        if weighted:  # sample / class weights: the native graph engine's weighted loss launch
+            return False, "sample weights"
         if model._regularized():  # weight penalties: the native graph engine's opt_step / reg_penalty
             return False, "regularizers"
         if model.optimizer.clipping()[0] is not None:  # the native graph engine's grad_norm / opt_step
@@ -424,7 +426,9 @@ class FusedConvNetEngine(Engine):
         self._ctrl_write(c)
 
     # --- data / epochs ---------------------------------------------------------------
-    def bind(self, x, y):
+    def bind(self, x, y, w=None):
+        if w is not None:
+            raise ValueError("the fused ConvNet engine takes no sample weights (eligible(..., weighted=True))")
         x = np.asarray(x)
         if tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28), (784,)):
             raise ValueError(f"fused ConvNet engine expects 28x28x1 inputs, got {x.shape[1:]}")

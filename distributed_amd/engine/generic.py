@@ -142,10 +142,10 @@ class GenericEngine(Engine):
             self.buckets.append((lo, hi, set(idxs)))
         self.bucket_of = {i: b for b, (_, _, idxs) in enumerate(self.buckets) for i in idxs}
 
-    def bind(self, x, y):
+    def bind(self, x, y, w=None):
         key = (id(x), id(y), len(x))
-        if self.feed is None or getattr(self, "_feed_key", None) != key:
-            self.feed = DataFeed(x, y, self.device)
+        if self.feed is None or getattr(self, "_feed_key", None) != key or not self.feed.same_weights(w):
+            self.feed = DataFeed(x, y, self.device, w=w)
             self._feed_key = key
         return self.feed
 
@@ -206,6 +206,10 @@ class GenericEngine(Engine):
                                   self.aug_seeds):
                 out = model(xb, training=True)
             ls = self.loss.per_sample(yb, out)
+            if feed.w is not None:
+                # sample / class weights: sum w_i l_i over the rows that exist; the count and
+                # the metrics stay unweighted (Keras SUM_OVER_BATCH_SIZE)
+                ls = ls * feed.w[idx]
             loss = ls.sum() * (1.0 / gcount)
             self._tick("forward")
             with torch.no_grad():

@@ -10,7 +10,9 @@ other model built from the supported layers.  What happens per step (one rank):
               (csrc/kernels/augment.hip; only for models that begin with such a chain)
     forward:  implicit-GEMM MFMA convs / dense (csrc/kernels/gemm.hip) with bias / ReLU /
               BatchNorm-statistics epilogues, fused BN(+residual)(+ReLU) apply, pooling
-    loss:     softmax cross-entropy + accuracy -> dlogits and the metric tail of G
+    loss:     softmax cross-entropy + accuracy -> dlogits and the metric tail of G (with
+              sample / class weights: each row's gradient and loss times the weight of its
+              sample, read from the epoch-ordered weights at the device cursor)
     backward: reverse plan: BN backward (3 passes), pooling backward, dgrad GEMMs
               (residual fan-in accumulated in the GEMM epilogue), wgrad GEMMs accumulated
               with fp32 atomics straight into the flat gradient buffer G (split-K)
@@ -269,8 +271,9 @@ class NativeGraphEngine(Engine):
         self._ctrl_write({C_IT: it})
 
     # --- data -------------------------------------------------------------------------------
-    def bind(self, x, y):
+    def bind(self, x, y, w=None):
         x = np.asarray(x)
+        sw = w  # per-sample loss weights (float32 [n]) or None
         h, w, c = self.in_shape
         if tuple(x.shape[1:]) not in ((h, w, c),) and not (c == 1 and tuple(x.shape[1:]) == (h, w)):
             raise ValueError(f"native graph engine expects inputs of shape {(h, w, c)}, got {x.shape[1:]}")
@@ -281,15 +284,18 @@ class NativeGraphEngine(Engine):
                                  f"(n, {self.K}) for this model, got y of shape {tuple(ys)}"
                                  " (to_categorical(y), or the sparse loss for class ids)")
         key = (id(x), id(y), len(x))
-        if self.feed is None or getattr(self, "_feed_key", None) != key:
+        if self.feed is None or getattr(self, "_feed_key", None) != key or not self.feed.same_weights(sw):
             torch.cuda.synchronize(self.device)
-            self.feed = DataFeed(x, y, self.device, flatten=True, allow_u8=env.get_bool("DAMD_X_U8", True))
+            self.feed = DataFeed(x, y, self.device, flatten=True, allow_u8=env.get_bool("DAMD_X_U8", True), w=sw)
             if self.dense_y and (self.feed.y.dtype != torch.float32 or tuple(self.feed.y.shape) !=
                                  (self.feed.n, self.K)):
                 raise ValueError(f"dense targets must be (n, {self.K}) numbers, got {tuple(self.feed.y.shape)}")
             self._feed_key = key
             self.x_ep = torch.empty_like(self.feed.x)
             self.y_ep = torch.empty_like(self.feed.y)
+            # the weights in epoch order beside x_ep / y_ep: the loss launch reads the row at
+            # the device cursor (None: the unweighted launch)
+            self.w_ep = torch.empty_like(self.feed.w) if self.feed.w is not None else None
             self.y_zero = torch.zeros(self.feed.n, dtype=torch.int32, device=self.device) if self.dense_y else None
             self.graph = None  # data pointers changed
             self._ctrl_write({C_NS: self.feed.n})
@@ -301,6 +307,8 @@ class NativeGraphEngine(Engine):
         perm = self.feed.perm.long()
         torch.index_select(self.feed.x, 0, perm, out=self.x_ep)
         torch.index_select(self.feed.y, 0, perm, out=self.y_ep)
+        if self.w_ep is not None:
+            torch.index_select(self.feed.w, 0, perm, out=self.w_ep)
         opt = self.model.optimizer
         self._ctrl_write({C_CUR: 0, C_AL: 0, C_AC: 0, C_AN: 0, C_WRAP: int(wrap_steps),
                           C_LR: _f2i(self._host_lr()), C_MOM: _f2i(getattr(opt, "momentum", 0.0)),
@@ -343,10 +351,11 @@ class NativeGraphEngine(Engine):
             # at the device cursor (self.labels: the 0 / -1 row validity gather_batch wrote)
             H.softmax_xent_dense(self.logits, self.y_ep, self.K, 1.0 / self.global_batch, self.dlogits,
                                  self.G[self.nparam:], label_smoothing=self.label_smoothing, labels=self.labels,
-                                 ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad)
+                                 ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad, weights=self.w_ep)
         else:
             H.softmax_xent(self.logits, self.labels, self.K, 1.0 / self.global_batch, self.dlogits,
-                           self.G[self.nparam:], ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad)
+                           self.G[self.nparam:], ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad,
+                           weights=self.w_ep)
         if self.reg_tab is not None:
             # loss sum += R(w) per valid local row (tail[2]), before the tail leaves with
             # bucket 0's all-reduce: the SUM over replicas yields R * (global rows)

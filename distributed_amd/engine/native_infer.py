@@ -14,7 +14,8 @@ every epoch).  Here that runs on the same lowered plan as training
   inference mode: pads as in training, crops centred, no flips;
 * one step = gather -> forward -> (``logits_store`` or, for a softmax output,
   ``softmax_store`` | ``softmax_xent`` or, for one-hot / dense targets,
-  ``softmax_xent_dense``) -> ``step_fold``
+  ``softmax_xent_dense``; with ``sample_weight`` either takes the staged weights and reads
+  the row at the device cursor) -> ``step_fold``
   (cursor + metric accumulators in the device ``Ctrl`` block), captured once as a HIP
   graph and replayed ceil(n / batch) times: no host synchronisation per batch, one at
   the end of the call.
@@ -112,21 +113,23 @@ class NativeInference:
                 C.logits_store(ex.logits.data_ptr(), ex.Kp, self.K, B, self.ctrl.data_ptr(),
                                self._bufs["out"].data_ptr(), s)
             C.step_fold(self.ctrl.data_ptr(), 0, s)
-        elif mode == "evaluate_dense":
+        elif mode.startswith("evaluate_dense"):
             # y: all-zero ids (gather_batch turns them into the 0 / -1 row validity); the
             # [n, K] target rows are read in place at the device cursor
             H.softmax_xent_dense(ex.logits, self._bufs["yd"], self.K, 1.0 / B, ex.dlogits, self.tail,
-                                 label_smoothing=self._eps, labels=ex.labels, ctrl=self.ctrl, rows=ex.xent_rows)
+                                 label_smoothing=self._eps, labels=ex.labels, ctrl=self.ctrl, rows=ex.xent_rows,
+                                 weights=self._bufs["w"] if mode.endswith("_w") else None)
             C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
         else:
             H.softmax_xent(ex.logits, ex.labels, self.K, 1.0 / B, ex.dlogits, self.tail, ctrl=self.ctrl,
-                           rows=ex.xent_rows)
+                           rows=ex.xent_rows, weights=self._bufs["w"] if mode.endswith("_w") else None)
             C.step_fold(self.ctrl.data_ptr(), self.tail.data_ptr(), s)
 
-    def _stage(self, x, y=None, dense=False):
+    def _stage(self, x, y=None, dense=False, sw=None):
         """Upload the call's inputs into (grown-only) device buffers; (re)capture happens
         only when a buffer had to be reallocated.  ``dense``: y holds [n, K] target rows,
-        kept as a float buffer (the class-id buffer is then all zeros)."""
+        kept as a float buffer (the class-id buffer is then all zeros).  ``sw``: per-sample
+        loss weights, float32 [n]."""
         n = len(x)
         h, w, c = self.in_shape
         x = np.asarray(x)
@@ -158,6 +161,15 @@ class NativeInference:
             self._bufs["y"].zero_()
         elif y is not None:
             self._bufs["y"][:n].copy_(torch.from_numpy(np.asarray(y).astype(np.int32).reshape(n)))
+        if sw is not None:
+            sw = np.ascontiguousarray(np.asarray(sw, dtype=np.float32).reshape(-1))
+            if sw.shape[0] != n:
+                raise ValueError(f"sample_weight has length {sw.shape[0]} but there are {n} samples")
+            wb = self._bufs.get("w")
+            if wb is None or wb.shape[0] < n:
+                self._bufs["w"] = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+                realloc = True
+            self._bufs["w"][:n].copy_(torch.from_numpy(sw))
         ob = self._bufs.get("out")
         if ob is None or ob.shape[0] < n:
             self._bufs["out"] = torch.zeros((max(n, 1), self.K), dtype=torch.float32, device=self.device)
@@ -196,10 +208,11 @@ class NativeInference:
         return self._bufs["out"][:n].cpu().numpy()
 
     @torch.no_grad()
-    def evaluate_sums(self, x, y) -> Tuple[float, float, float]:
-        """(sum of per-sample loss, number of samples, number correct) over (x, y)."""
+    def evaluate_sums(self, x, y, sample_weight=None) -> Tuple[float, float, float]:
+        """(sum of per-sample loss, number of samples, number correct) over (x, y); with
+        ``sample_weight`` (float32 [n]) the sum of w_i * loss_i, the two counts unweighted."""
         dense = dense_targets(self.model)
-        n = self._stage(x, y, dense=dense)
+        n = self._stage(x, y, dense=dense, sw=sample_weight)
         if n == 0:
             return 0.0, 0.0, 0.0
         if dense:
@@ -207,7 +220,8 @@ class NativeInference:
             if eps != getattr(self, "_eps", None):  # a kernel argument of the captured step
                 self._eps = eps
                 self._graphs.pop("evaluate_dense", None)
-        self._run("evaluate_dense" if dense else "evaluate", n)
+                self._graphs.pop("evaluate_dense_w", None)
+        self._run(("evaluate_dense" if dense else "evaluate") + ("_w" if sample_weight is not None else ""), n)
         c = self.ctrl.cpu().tolist()
         loss, cnt = _i2f(c[C_AL]), _i2f(c[C_AN])
         p = self.params

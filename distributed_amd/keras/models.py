@@ -37,6 +37,7 @@ from . import losses as _losses
 from . import metrics as _metrics
 from . import optimizers as _opts
 from . import regularizers as _regs
+from .utils import resolve_sample_weights as _resolve_weights
 
 KERAS_VERSION = "2.2.4-tf"
 
@@ -200,16 +201,17 @@ class Model(L.Layer):
         return ["loss"] + [m.name for m in self.compiled_metrics]
 
     # --- engine ----------------------------------------------------------------------
-    def _get_engine(self, per_replica, global_batch):
+    def _get_engine(self, per_replica, global_batch, weighted=False):
         from ..engine import select_engine
 
-        # (a learning-rate schedule coming or going changes which engines are eligible)
+        # (a learning-rate schedule coming or going, or sample weights, change which engines
+        # are eligible)
         key = (per_replica, global_batch, id(self._strategy), id(self.optimizer), id(self.loss),
-               isinstance(self.optimizer.learning_rate, float))
+               isinstance(self.optimizer.learning_rate, float), bool(weighted))
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.finish()
-            self._engine = select_engine(self, self._strategy, per_replica, global_batch)
+            self._engine = select_engine(self, self._strategy, per_replica, global_batch, weighted=bool(weighted))
             self._engine_key = key
         return self._engine
 
@@ -219,8 +221,6 @@ class Model(L.Layer):
             steps_per_epoch=None, validation_steps=None, validation_freq=1, **kw):
         if self.optimizer is None or self.loss is None:
             raise RuntimeError("You must compile your model before training/testing.")
-        if class_weight is not None or sample_weight is not None:
-            raise NotImplementedError("class_weight / sample_weight are not supported")
         st = self._strategy
         world = st.num_replicas_in_sync
         batch_size = int(batch_size or 32)
@@ -229,10 +229,16 @@ class Model(L.Layer):
         per = batch_size // world
         x = np.asarray(x)
         y = np.asarray(y)
+        # class_weight / sample_weight -> one float32 weight per sample (or None); it belongs to
+        # the sample: sliced by validation_split with x and y, permuted and sharded with them
+        w = _resolve_weights(y, class_weight, sample_weight, len(x))
         if validation_split and validation_data is None:
             k = int(len(x) * (1 - validation_split))
-            validation_data = (x[k:], y[k:])
+            validation_data = (x[k:], y[k:]) if w is None else (x[k:], y[k:], w[k:])
             x, y = x[:k], y[:k]
+            w = None if w is None else np.ascontiguousarray(w[:k])
+        if validation_data is not None and len(validation_data) not in (2, 3):
+            raise ValueError("validation_data must be (x, y) or (x, y, sample_weight)")
         n = len(x)
         steps = int(steps_per_epoch) if steps_per_epoch else int(math.ceil(n / batch_size))
         if isinstance(st, MultiWorkerMirroredStrategy):
@@ -240,8 +246,11 @@ class Model(L.Layer):
             if not any(isinstance(c, (cbks.ModelCheckpoint, cbks.BackupAndRestore)) for c in (callbacks or [])):
                 dlog.warning("ModelCheckpoint callback is not provided. Workers will need to restart training if "
                              "any fails.")
-        engine = self._get_engine(per, batch_size)
-        engine.bind(x, y)
+        engine = self._get_engine(per, batch_size, weighted=w is not None)
+        if w is None:
+            engine.bind(x, y)
+        else:
+            engine.bind(x, y, w)
         hist = cbks.History()
         cb_list = [hist]
         if verbose:
@@ -325,7 +334,7 @@ class Model(L.Layer):
                     recoveries += 1
                     dlog.warning("epoch %d: %s; re-running it", epoch + 1, e)
                     engine = self._engine = engine.rebuild_after_fault(snap)
-                    engine.bind(x, y)
+                    engine.bind(x, y)  # (the fused engine: never a weighted fit)
                     global_step = step0
                     continue
                 self.sync_on_read_variables()  # BN moving statistics: replica mean (all ranks)
@@ -334,7 +343,8 @@ class Model(L.Layer):
                 logs["seen"] = min(done * batch_size, n) if steps_per_epoch is None else done * batch_size
                 if validation_data is not None and (epoch + 1) % validation_freq == 0:
                     vres = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, verbose=0,
-                                         steps=validation_steps, _return_dict=True)
+                                         steps=validation_steps, _return_dict=True,
+                                         sample_weight=validation_data[2] if len(validation_data) > 2 else None)
                     logs.update({"val_" + k: v for k, v in vres.items()})
                 cl.on_epoch_end(epoch, {k: v for k, v in logs.items()})
                 if mirror_every and (epoch + 1) % mirror_every == 0:
@@ -398,15 +408,18 @@ class Model(L.Layer):
         return torch.cat(outs).numpy() if outs else np.zeros((0,))
 
     @torch.no_grad()
-    def evaluate(self, x=None, y=None, batch_size=None, verbose=1, steps=None, return_dict=False, _return_dict=False):
+    def evaluate(self, x=None, y=None, batch_size=None, verbose=1, steps=None, return_dict=False, _return_dict=False,
+                 sample_weight=None):
         """Loss and metrics over (x, y).  Under a multi-worker strategy each worker
-        evaluates a disjoint shard and the sums are all-reduced."""
+        evaluates a disjoint shard and the sums are all-reduced.  ``sample_weight`` (length
+        n, 1-D or (n, 1)): the loss is sum w_i l_i / n; the metrics stay unweighted."""
         self._sync_engine()
         st = self._strategy
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = x.astype(np.float32, copy=False)
         y = np.asarray(y)
+        w = _resolve_weights(y, None, sample_weight, len(x))
         world, rank = st.num_replicas_in_sync, st.rank
         bs = int(batch_size or 32)
         n = len(x) if steps is None else min(len(x), int(steps) * bs)
@@ -416,7 +429,10 @@ class Model(L.Layer):
         plan = self._native_infer(bs, evaluate=True)
         if plan is not None:
             # one upload, a graph replay per batch, one host sync for the whole shard
-            loss_sum, cnt_, correct = plan.evaluate_sums(x[lo:hi], y[lo:hi])
+            if w is None:
+                loss_sum, cnt_, correct = plan.evaluate_sums(x[lo:hi], y[lo:hi])
+            else:
+                loss_sum, cnt_, correct = plan.evaluate_sums(x[lo:hi], y[lo:hi], sample_weight=w[lo:hi])
             sums[0], sums[1] = loss_sum, cnt_
             for k in range(len(self.compiled_metrics)):
                 sums[2 + k] = correct
@@ -425,7 +441,10 @@ class Model(L.Layer):
             xb = torch.from_numpy(np.ascontiguousarray(x[i:j])).to(dev).float()
             yb = torch.from_numpy(np.ascontiguousarray(y[i:j])).to(dev)
             out = self(xb, training=False)
-            sums[0] += float(self.loss.per_sample(yb, out).double().sum())
+            ls = self.loss.per_sample(yb, out)
+            if w is not None:
+                ls = ls * torch.from_numpy(w[i:j]).to(dev)
+            sums[0] += float(ls.double().sum())
             sums[1] += j - i
             for k, m in enumerate(self.compiled_metrics):
                 sums[2 + k] += float(m.per_sample(yb, out).double().sum())

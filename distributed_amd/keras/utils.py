@@ -97,3 +97,63 @@ def to_categorical(y, num_classes=None, dtype="float32"):
     out = np.zeros((y.shape[0], n), dtype=dtype)
     out[np.arange(y.shape[0]), y] = 1
     return out
+
+
+def resolve_sample_weights(y, class_weight=None, sample_weight=None, n=None):
+    """The one per-sample weight array of ``fit`` / ``evaluate``: float32 ``[n]``, or None
+    when neither argument is given.  Every engine consumes only this array.
+
+    ``class_weight``: a dict whose keys are exactly ``0 .. C-1`` (the tf.keras rule); sample
+    i gets ``class_weight[y_i]``, the class of a one-hot / dense target row being its argmax
+    (ties to the smallest index).  ``sample_weight``: array-like of length ``n``, 1-D or
+    ``(n, 1)``, every entry finite.  Both: their product.  Anything else is a ValueError."""
+    if class_weight is None and sample_weight is None:
+        return None
+    y = np.asarray(y)
+    n = int(len(y) if n is None else n)
+    w = np.ones(n, dtype=np.float32)
+    if class_weight is not None:
+        if not isinstance(class_weight, dict) or not class_weight:
+            raise ValueError("class_weight must be a dict {class id: weight}")
+        try:
+            cw = {int(k): float(v) for k, v in class_weight.items()}
+        except (TypeError, ValueError):
+            raise ValueError(f"class_weight keys must be class ids and its values numbers, got {class_weight!r}")
+        C = len(cw)
+        if len(cw) != len(class_weight) or sorted(cw) != list(range(C)):
+            raise ValueError(f"class_weight keys must be exactly 0 .. {C - 1} (one per class), got "
+                             f"{sorted(class_weight, key=str)}")
+        table = np.array([cw[c] for c in range(C)], dtype=np.float32)
+        if not np.isfinite(table).all():
+            raise ValueError("class_weight holds a value that is not a finite number")
+        if len(y) != n:
+            raise ValueError(f"class_weight: y has {len(y)} rows, expected {n}")
+        if y.ndim > 1 and y.shape[-1] > 1:
+            ids = y.reshape(n, -1).argmax(axis=1)  # (first maximum: ties to the smallest index)
+        else:
+            ids = y.reshape(n)
+            if not np.issubdtype(ids.dtype, np.integer):
+                if not np.array_equal(ids, np.rint(ids)):
+                    raise ValueError("class_weight needs class-id or one-hot targets")
+                ids = ids.astype(np.int64)
+        bad = (ids < 0) | (ids >= C)
+        if bad.any():
+            raise ValueError(f"class_weight has the classes 0 .. {C - 1} but y holds the label "
+                             f"{int(ids[bad][0])}")
+        w *= table[ids]
+    if sample_weight is not None:
+        try:
+            sw = np.asarray(sample_weight, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("sample_weight must be an array of numbers")
+        if sw.ndim == 2 and sw.shape[1] == 1:
+            sw = sw[:, 0]
+        if sw.ndim != 1:
+            raise ValueError(f"sample_weight must have shape ({n},) or ({n}, 1), got {tuple(sw.shape)} "
+                             "(temporal 2-D sample weights are not supported)")
+        if sw.shape[0] != n:
+            raise ValueError(f"sample_weight has length {sw.shape[0]} but there are {n} samples")
+        if not np.isfinite(sw).all():
+            raise ValueError("sample_weight holds a NaN or an infinite entry")
+        w *= sw.astype(np.float32)
+    return np.ascontiguousarray(w, dtype=np.float32)

@@ -1234,13 +1234,32 @@ def xent_rows(B: int, device) -> torch.Tensor:
     return torch.zeros(3 * B + 1, dtype=torch.float32, device=device)
 
 
-def softmax_xent(logits, labels, K, scale, dlogits, tail, ctrl=None, rows=None, bias_grad=None):
+def _chk_loss_weights(weights, B, ctrl, where):
+    """Per-row loss weights: fp32, contiguous, 1-D; one per logits row without ``ctrl`` (with
+    it the kernel indexes the epoch-ordered array at the device cursor)."""
+    if weights.dtype != torch.float32:
+        raise ValueError(f"{where}: weights must be float32, got {weights.dtype}")
+    if weights.dim() != 1 or not weights.is_contiguous():
+        raise ValueError(f"{where}: weights must be a contiguous 1-D tensor")
+    if not weights.is_cuda:
+        raise ValueError(f"{where}: weights must be a device tensor")
+    if ctrl is None and weights.numel() < B:
+        raise ValueError(f"{where}: {B} logits rows but {weights.numel()} weights")
+
+
+def softmax_xent(logits, labels, K, scale, dlogits, tail, ctrl=None, rows=None, bias_grad=None, weights=None):
     """ctrl (the engine's device control block) makes the scale 1 / real rows of the global
     batch; labels < 0 mark padding rows of a short final batch.  The loss / correct / count
     sums are formed in a fixed row order (``rows``: :func:`xent_rows` scratch).
     ``bias_grad`` (fp32 [K], optional; needs :func:`softmax_bias_fold_ok`): += the column
-    sums of dlogits, bitwise as :func:`colsum` would add them."""
+    sums of dlogits, bitwise as :func:`colsum` would add them.
+    ``weights`` (fp32, optional): a row's dlogits and loss are multiplied by its weight, the
+    correct / count sums are not.  Without ``ctrl`` row b has ``weights[b]``; with it the
+    weight of the sample at the device cursor, ``weights[cursor * global_batch + row0 + b]``
+    (modulo nsamples in wrap mode).  A row with label < 0 never reads the array."""
     B, ld = logits.shape
+    if weights is not None:
+        _chk_loss_weights(weights, B, ctrl, "softmax_xent")
     if rows is None:
         rows = xent_rows(B, logits.device)  # (eager callers only: engines pass their own)
     if bias_grad is not None:
@@ -1248,18 +1267,21 @@ def softmax_xent(logits, labels, K, scale, dlogits, tail, ctrl=None, rows=None, 
         if bias_grad.numel() < K or not softmax_bias_fold_ok(B, K):
             raise ValueError("softmax_xent: bias_grad needs >= K floats and a one-split colsum shape")
     _C().softmax_xent(_ptr(logits), ld, _ptr(labels), B, K, float(scale), _ptr(ctrl), _ptr(dlogits), _ptr(tail),
-                      _ptr(rows), stream_handle(), bias_grad=_ptr(bias_grad))
+                      _ptr(rows), stream_handle(), bias_grad=_ptr(bias_grad), weights=_ptr(weights))
 
 
 def softmax_xent_dense(logits, targets, K, scale, dlogits, tail, label_smoothing=0.0, labels=None, ctrl=None,
-                       rows=None, bias_grad=None):
+                       rows=None, bias_grad=None, weights=None):
     """:func:`softmax_xent` against dense fp32 target rows ``[n, K]`` (one-hot or soft) with
     Keras label smoothing: loss = -sum y' log softmax, dlogits = (softmax * sum y' - y') *
     scale, correct = argmax logits == argmax targets.  Without ``ctrl`` row b of ``targets``
     belongs to logits row b; with ``ctrl`` the kernel reads row ``cursor * global_batch +
     row0 + b`` of the epoch-ordered targets (modulo nsamples in wrap mode) and ``labels``
-    (int32 [B], >= 0 real / < 0 past the end of the data) is required."""
+    (int32 [B], >= 0 real / < 0 past the end of the data) is required.  ``weights``: as
+    :func:`softmax_xent`, indexed by the target row."""
     B, ld = logits.shape
+    if weights is not None:
+        _chk_loss_weights(weights, B, ctrl, "softmax_xent_dense")
     _chk(logits, torch.float32, "logits")
     _chk(targets, torch.float32, "targets")
     if targets.dim() != 2 or targets.shape[1] != K:
@@ -1285,7 +1307,7 @@ def softmax_xent_dense(logits, targets, K, scale, dlogits, tail, label_smoothing
             raise ValueError("softmax_xent_dense: bias_grad needs >= K floats and a one-split colsum shape")
     _C().softmax_xent_dense(_ptr(logits), ld, _ptr(labels), _ptr(targets), B, K, float(label_smoothing), float(scale),
                             _ptr(ctrl), _ptr(dlogits), _ptr(tail), _ptr(rows), stream_handle(),
-                            bias_grad=_ptr(bias_grad))
+                            bias_grad=_ptr(bias_grad), weights=_ptr(weights))
 
 
 def softmax_store(logits, K, ctrl, out):

@@ -200,18 +200,22 @@ def lr_schedule32(schedule, step) -> float:
     return float(init * ((f(1) - a) * f(0.5) * (f(1) + c) + a))
 
 
-def sparse_softmax_xent(logits, labels):
-    """Per-sample loss of SparseCategoricalCrossentropy(from_logits=True)."""
-    return F.cross_entropy(logits.float(), labels.long(), reduction="none")
+def sparse_softmax_xent(logits, labels, weights=None):
+    """Per-sample loss of SparseCategoricalCrossentropy(from_logits=True); with ``weights``
+    (one per row) each row's loss times its weight."""
+    ls = F.cross_entropy(logits.float(), labels.long(), reduction="none")
+    return ls if weights is None else ls * weights.to(ls.dtype)
 
 
-def softmax_xent_dense(logits, targets, label_smoothing=0.0):
+def softmax_xent_dense(logits, targets, label_smoothing=0.0, weights=None):
     """Per-sample loss of CategoricalCrossentropy(from_logits=True, label_smoothing) against
-    dense target rows: -(y' * log_softmax(z)).sum(-1), y' = y (1 - eps) + eps / K."""
+    dense target rows: -(y' * log_softmax(z)).sum(-1), y' = y (1 - eps) + eps / K; with
+    ``weights`` (one per row) each row's loss times its weight."""
     y = targets.float()
     if label_smoothing:
         y = y * (1.0 - label_smoothing) + label_smoothing / y.shape[-1]
-    return -(y * torch.log_softmax(logits.float(), dim=-1)).sum(-1)
+    ls = -(y * torch.log_softmax(logits.float(), dim=-1)).sum(-1)
+    return ls if weights is None else ls * weights.to(ls.dtype)
 
 
 def categorical_accuracy(logits, targets):

@@ -209,17 +209,37 @@ def compile(object, optimizer=None, loss=None, metrics=None, **kw):  # noqa: A00
 
 
 def fit(object, x=None, y=None, batch_size=None, epochs=10, verbose=1, callbacks=None, steps_per_epoch=None,
-        validation_split=0.0, validation_data=None, shuffle=True, initial_epoch=0, **kw):
+        validation_split=0.0, validation_data=None, shuffle=True, initial_epoch=0, class_weight=None,
+        sample_weight=None, **kw):
     """R ``fit`` (note: R keras defaults epochs = 10).  Returns the History; the R
-    accessor ``result$metrics$accuracy`` is ``History.metrics['accuracy']``."""
+    accessor ``result$metrics$accuracy`` is ``History.metrics['accuracy']``.
+    ``class_weight``: an R named list arrives as a dict with string names, ``{"0": 1, "1":
+    2.5}``; the names become the integer class ids."""
+    if class_weight is not None:
+        class_weight = _class_weight_ids(class_weight)
     return object.fit(x, y, batch_size=None if batch_size is None else int(batch_size), epochs=int(epochs),
                       verbose=verbose, callbacks=callbacks, steps_per_epoch=steps_per_epoch,
                       validation_split=validation_split, validation_data=validation_data, shuffle=shuffle,
-                      initial_epoch=initial_epoch, **kw)
+                      initial_epoch=initial_epoch, class_weight=class_weight, sample_weight=sample_weight, **kw)
 
 
-def evaluate(object, x, y, batch_size=None, verbose=1):
-    return object.evaluate(x, y, batch_size=batch_size, verbose=verbose)
+def _class_weight_ids(class_weight):
+    if not isinstance(class_weight, dict):
+        raise ValueError("class_weight must be a named list: list(\"0\" = 1, \"1\" = 2.5)")
+    out = {}
+    for k, v in class_weight.items():
+        try:
+            i = int(str(k).strip()) if isinstance(k, str) else int(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"class_weight names must be class ids (\"0\", \"1\", ...), got {k!r}")
+        if i in out:
+            raise ValueError(f"class_weight names class {i} twice")
+        out[i] = v
+    return out
+
+
+def evaluate(object, x, y, batch_size=None, verbose=1, sample_weight=None):
+    return object.evaluate(x, y, batch_size=batch_size, verbose=verbose, sample_weight=sample_weight)
 
 
 def predict(object, x, batch_size=None):

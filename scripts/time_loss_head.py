@@ -11,6 +11,13 @@ machine state.  Reported per kernel: the median over the rounds and its run-to-r
 
     python scripts/time_loss_head.py --shape 64,1000,1000 --shape 64,10,16
     python scripts/time_loss_head.py --sparse-only     # a tree without the dense kernel
+    python scripts/time_loss_head.py --weighted        # both kernels with per-row weights
+
+``--weighted`` times the W = true instantiations instead (keys ``<kernel>+w``): the same two
+launches with a ``weights=`` array of B distinct values, in the same two-graph alternation.
+Compare it with a run without the flag in the same session: what a graph measures depends on
+which graphs it alternates with (all four in one process put 0.07 us on the unweighted sparse
+kernel at 64 x 1000 and took 0.05 us off the weighted one), so the two arms are two runs.
 """
 import argparse
 import json
@@ -46,7 +53,7 @@ def _time(g, launches):
     return a.elapsed_time(b) * 1e3 / launches  # us per launch
 
 
-def measure(H, B, K, ld, eps, launches, rounds, warmup, sparse_only):
+def measure(H, B, K, ld, eps, launches, rounds, warmup, sparse_only, weighted=False):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(0)
     z = torch.randn(B, ld, generator=gen).to(dev)
@@ -57,10 +64,14 @@ def measure(H, B, K, ld, eps, launches, rounds, warmup, sparse_only):
     tail = torch.zeros(3, device=dev)
     rows = H.xent_rows(B, dev)
     bg = torch.zeros(K, device=dev) if H.softmax_bias_fold_ok(B, K) else None
-    runs = {"softmax_xent": lambda: H.softmax_xent(z, lab, K, 1.0 / B, dl, tail, rows=rows, bias_grad=bg)}
+    # (the unweighted launches pass no weights argument: the script also runs on trees without one)
+    kw, tag = {}, ""
+    if weighted:
+        kw, tag = {"weights": (0.25 + 0.05 * torch.arange(B, dtype=torch.float32)).to(dev)}, "+w"
+    runs = {"softmax_xent" + tag: lambda: H.softmax_xent(z, lab, K, 1.0 / B, dl, tail, rows=rows, bias_grad=bg, **kw)}
     if not sparse_only:
-        runs["softmax_xent_dense"] = lambda: H.softmax_xent_dense(z, y, K, 1.0 / B, dl, tail, label_smoothing=eps,
-                                                                  rows=rows, bias_grad=bg)
+        runs["softmax_xent_dense" + tag] = lambda: H.softmax_xent_dense(z, y, K, 1.0 / B, dl, tail, label_smoothing=eps,
+                                                                        rows=rows, bias_grad=bg, **kw)
     graphs = {k: _graph_of(fn, launches) for k, fn in runs.items()}
     for _ in range(warmup):
         for g in graphs.values():
@@ -86,6 +97,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sparse-only", action="store_true")
+    ap.add_argument("--weighted", action="store_true", help="time both kernels with per-row weights")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_loss_head.py needs a HIP device")
@@ -93,7 +105,8 @@ def main():
 
     shapes = [tuple(int(v) for v in s.split(",")) for s in (a.shape or ["64,1000,1000", "64,10,16"])]
     for B, K, ld in shapes:
-        print(json.dumps(measure(H, B, K, ld, a.label_smoothing, a.launches, a.rounds, a.warmup, a.sparse_only)),
+        print(json.dumps(measure(H, B, K, ld, a.label_smoothing, a.launches, a.rounds, a.warmup, a.sparse_only,
+                                 a.weighted)),
               flush=True)
 
 
