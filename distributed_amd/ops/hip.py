@@ -87,15 +87,21 @@ def tile_rows(tile: int) -> int:
     return 256 if tile == 1 else 128
 
 
-def pick_splits(M: int, N: int, K: int, tile: int, target_wg: int = 1024) -> Tuple[int, int]:
-    """Split-K factor so a long-K product still launches >> 256 workgroups (256 CUs)."""
+def tile_count(M: int, N: int, tile: int) -> int:
+    """Output tiles (= workgroups per K split) of an [M,N] product."""
     bm, bn = (256, 64) if tile == 1 else (128, 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    splits = max(1, min(-(-target_wg // tiles), max(1, K // 256)))
-    kps = -(-K // splits)
-    kps = -(-kps // BK) * BK
-    splits = -(-K // kps)
-    return splits, kps
+    return -(-M // bm) * -(-N // bn)
+
+
+def split_k(K: int, tiles: int, target: int, unit: int, limit: int) -> Tuple[int, int]:
+    """The split-K rule of every plan below: (splits, k_per_split) of a product summed over K
+    whose grid of ``tiles`` workgroups leaves CUs idle.  Enough splits to launch ``target``
+    workgroups, at most ``limit`` (the caller's minimum depth per split and slab cap; < 1
+    counts as 1); K is cut in multiples of ``unit`` (the kernel's k-step) and splits that
+    would be empty after the rounding are dropped."""
+    splits = max(1, min(-(-target // tiles), limit))
+    kps = -(-(-(-K // unit)) // splits) * unit
+    return -(-K // kps), kps
 
 
 # weight-gradient split-K: every split stores its fp32 partial tile to a slab and one
@@ -105,16 +111,16 @@ WGRAD_TARGET_WG = int(os.environ.get("DAMD_WGRAD_TARGET_WG", 512))  # 2 workgrou
 WGRAD_SLAB_MAX = 64 << 20      # bytes of slab per GEMM
 
 
+def slab_cap(M: int, N: int) -> int:
+    """Most fp32 [M,N] slabs one GEMM may write (WGRAD_SLAB_MAX bytes; at least one)."""
+    return max(1, WGRAD_SLAB_MAX // (M * N * 4))
+
+
 def wgrad_plan(M: int, N: int, K: int) -> Tuple[int, int, int]:
     """(tile, splits, k_per_split) of a weight-gradient GEMM [M,N] summed over K."""
     t = pick_tile(N)
-    bm, bn = (256, 64) if t == 1 else (128, 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    cap = max(1, WGRAD_SLAB_MAX // (M * N * 4))
-    splits = max(1, min(-(-WGRAD_TARGET_WG // tiles), max(1, K // 256), cap))
-    kps = -(-K // splits)
-    kps = -(-kps // BK) * BK
-    return t, -(-K // kps), kps
+    splits, kps = split_k(K, tile_count(M, N, t), WGRAD_TARGET_WG, BK, min(max(1, K // 256), slab_cap(M, N)))
+    return t, splits, kps
 
 
 # bf16-output GEMMs (conv fwd / dgrad) whose tile count leaves CUs idle are split over K
@@ -128,34 +134,26 @@ FINISH_RB = 16
 def split_plan(M: int, N: int, K: int, tile: int, bk: int = BK) -> Tuple[int, int]:
     """(splits, k_per_split) for a bf16-output GEMM; splits == 1: the fused epilogue.
     k_per_split is a multiple of the kernel's k-step ``bk``."""
-    bm, bn = (256, 64) if tile == 1 else (128, 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    kfull = -(-K // bk) * bk
+    tiles = tile_count(M, N, tile)
     if tiles >= SPLIT_MIN_TILES:
-        return 1, kfull
-    cap = max(1, WGRAD_SLAB_MAX // (M * N * 4))
-    splits = max(1, min(-(-SPLIT_TARGET_WG // tiles), K // (BK * 8), cap))
-    if splits == 1:
-        return 1, kfull
-    kps = -(-K // splits)
-    kps = -(-kps // bk) * bk
-    return -(-K // kps), kps
+        return 1, -(-K // bk) * bk
+    return split_k(K, tiles, SPLIT_TARGET_WG, bk, min(K // 256, slab_cap(M, N)))
 
 
-def _wgrad_slab1(M: int, N: int, K: int) -> bool:
-    """An unsplit weight-gradient GEMM over few tiles (the classifier's dW: 32 tiles, K =
-    batch): plain stores to one slab + the flat reduce beat the atomic epilogue there
-    (fp32 atomics measured 19 us for the 512 x 1000 dW)."""
-    t, splits, _ = wgrad_plan(M, N, K)
-    bm, bn = (256, 64) if t == 1 else (128, 128)
-    return splits == 1 and -(-M // bm) * -(-N // bn) <= 64 and (M * N) % 4 == 0 and M * N >= 4 * 8192
+def dense_wgrad_plan(M: int, N: int, K: int) -> dict:
+    """Launch plan of the dense weight gradient dw[M,N] summed over K (= batch), in
+    conv_wgrad_plan's form: wgrad_plan's tile / splits / kps, the fp32 workspace ``ws`` and
+    ``slab1``: an unsplit GEMM over few tiles (the classifier's dW: 32 tiles) stores to one
+    slab that the flat reduce adds -- that beats the atomic epilogue there (fp32 atomics
+    measured 19 us for the 512 x 1000 dW)."""
+    t, splits, kps = wgrad_plan(M, N, K)
+    slab1 = splits == 1 and tile_count(M, N, t) <= 64 and (M * N) % 4 == 0 and M * N >= 4 * 8192
+    return {"amode": A_MC, "M": M, "N": N, "K": K, "tile": t, "splits": splits, "kps": kps, "kstep": 0,
+            "slab1": slab1, "ws": splits * M * N if splits > 1 or slab1 else 0}
 
 
 def wgrad_workspace_elems(M: int, N: int, K: int) -> int:
-    _, splits, _ = wgrad_plan(M, N, K)
-    if splits == 1 and _wgrad_slab1(M, N, K):
-        return M * N
-    return splits * M * N if splits > 1 else 0
+    return dense_wgrad_plan(M, N, K)["ws"]
 
 
 def wgrad64_geo(n: int, ho: int, wo: int, kb: int) -> Tuple[int, int]:
@@ -178,73 +176,57 @@ def wgrad3_ok(n, h, w, cin, cout, k, s, pad) -> bool:
 def conv_wgrad_plan(x_shape, w_shape, strides=(1, 1), padding="valid") -> dict:
     """Launch plan of conv_wgrad.  3x3/stride-1/pad-1 layers with channels % 64 == 0: the
     direct kernel (conv_wgrad3.hip, all nine taps per block).  Otherwise the LDS-DMA
-    kernel over virtual rows (conv_gemm.hip) for layers with N = Cout > 64, k-step 32 for images of <= 16 columns (4 blocks/CU:
-    the small-image layers are bound by per-block overheads) else 64; the register-staged
-    kernel over pixels for N <= 64 (measured faster there: scripts/bench_gemm.py)."""
+    kernel over virtual rows (conv_gemm.hip) for the packed-tap stem and for layers with
+    N = Cout > 64, k-step 32 for images of <= 16 columns (4 blocks/CU: the small-image
+    layers are bound by per-block overheads) else 64; the register-staged kernel over
+    pixels for N <= 64 (measured faster there: scripts/bench_gemm.py)."""
     n, h, wd, cin, ho, wo, kh, kw, s, pad, cout = conv_geo(x_shape, w_shape, strides, padding)
     M, N = kh * kw * cin, cout
-    kb = int(os.environ.get("DAMD_CONV_KB", "0")) or (32 if wo <= 16 else 64)
-    vr, g = wgrad64_geo(n, ho, wo, kb)
-    if stem4_ok(x_shape, w_shape, strides, padding):
-        # packed-tap stem: M = KH x 8 x 4 rows of the stem4_weight_shape layout
-        M = kh * 32
-        t = pick_tile(N)
-        bm, bn = (256, 64) if t == 1 else (128, 128)
-        tiles = -(-M // bm) * -(-N // bn)
-        steps = -(-vr // g)
-        cap = max(1, WGRAD_SLAB_MAX // (M * N * 4))
-        splits = max(1, min(-(-WGRAD_TARGET_WG // tiles), max(1, steps // 4), cap))
-        kps = -(-steps // splits) * g
-        splits = -(-vr // kps)
-        return {"amode": A_WGRAD64, "M": M, "N": N, "K": vr, "tile": t, "splits": splits, "kps": kps, "kstep": kb,
-                "ws": splits * M * N if splits > 1 else 0}
+    stem = stem4_ok(x_shape, w_shape, strides, padding)
     pick = os.environ.get("DAMD_WGRAD_KERNEL", "auto")  # auto | direct | glds | reg (tests, A/B runs)
     dma = os.environ.get("DAMD_CONV_GLDS", "1") != "0"
-    if dma and pick in ("auto", "direct") and wgrad3_ok(n, h, wd, cin, cout, kh, s, pad):
+    kstep = 0
+    if not stem and dma and pick in ("auto", "direct") and wgrad3_ok(n, h, wd, cin, cout, kh, s, pad):
         # direct 3x3 kernel (csrc/kernels/conv_wgrad3.hip): 64x64 (ci, co) tiles x all 9 taps
-        Q = n * (h + 1) * (wd + 1)
-        tiles = (cin // 64) * (cout // 64)
-        steps = -(-Q // 32)
-        cap = max(1, WGRAD_SLAB_MAX // (M * N * 4))
+        amode, t, K = A_WGRAD3, 0, n * (h + 1) * (wd + 1)
         target = int(os.environ.get("DAMD_WGRAD3_WG", "256"))  # 8-9-wave blocks, 1 per CU
-        splits = max(1, min(-(-target // tiles), max(1, steps // 8), cap))
-        kps = -(-steps // splits) * 32
-        splits = -(-Q // kps)
-        return {"amode": A_WGRAD3, "M": M, "N": N, "K": Q, "tile": 0, "splits": splits, "kps": kps, "kstep": 0,
-                "ws": splits * M * N if splits > 1 else 0}
-    glds = N > 64 if pick == "auto" else pick == "glds"
-    if os.environ.get("DAMD_CONV_GLDS", "1") != "0" and glds and vr < (1 << 21):
+        splits, kps = split_k(K, (cin // 64) * (cout // 64), target, 32,
+                              min(max(1, -(-K // 32) // 8), slab_cap(M, N)))
+    else:
+        kb = int(os.environ.get("DAMD_CONV_KB", "0")) or (32 if wo <= 16 else 64)
+        vr, g = wgrad64_geo(n, ho, wo, kb)
         t = pick_tile(N)
-        bm, bn = (256, 64) if t == 1 else (128, 128)
-        tiles = -(-M // bm) * -(-N // bn)
-        steps = -(-vr // g)
-        cap = max(1, WGRAD_SLAB_MAX // (M * N * 4))
-        splits = max(1, min(-(-WGRAD_TARGET_WG // tiles), max(1, steps // 4), cap))
-        kps = -(-steps // splits) * g
-        splits = -(-vr // kps)
-        return {"amode": A_WGRAD64, "M": M, "N": N, "K": vr, "tile": t, "splits": splits, "kps": kps, "kstep": kb,
-                "ws": splits * M * N if splits > 1 else 0}
-    K = n * ho * wo
-    t, splits, kps = wgrad_plan(M, N, K)
-    return {"amode": A_WGRAD, "M": M, "N": N, "K": K, "tile": t, "splits": splits, "kps": kps, "kstep": 0,
+        if stem or (dma and (N > 64 if pick == "auto" else pick == "glds") and vr < (1 << 21)):
+            if stem:  # packed taps: M = KH x 8 x 4 rows of the stem4_weight_shape layout
+                M = kh * 32
+            amode, K, kstep = A_WGRAD64, vr, kb
+            splits, kps = split_k(K, tile_count(M, N, t), WGRAD_TARGET_WG, g,
+                                  min(max(1, -(-K // g) // 4), slab_cap(M, N)))
+        else:
+            amode, K = A_WGRAD, n * ho * wo
+            t, splits, kps = wgrad_plan(M, N, K)
+    return {"amode": amode, "M": M, "N": N, "K": K, "tile": t, "splits": splits, "kps": kps, "kstep": kstep,
             "ws": splits * M * N if splits > 1 else 0}
 
 
-def _wgrad_gemm(A, B, dw, workspace, *, amode, M, N, K, lda=0, ldb=0, geo=(), accumulate=True):
-    t, splits, kps = wgrad_plan(M, N, K)
-    if splits == 1 and not (_wgrad_slab1(M, N, K) and workspace is not None and workspace.numel() >= M * N):
-        # one writer per element: the atomic epilogue is an uncontended add
+def _wgrad_launch(A, B, dw, ws, plan, *, lda=0, ldb=0, geo=(), accumulate=True, slab1=False, reduce=None):
+    """The weight-gradient GEMM dw[M,N] (+)= A^T B of ``plan`` (conv_wgrad_plan /
+    dense_wgrad_plan).  One split: the atomic epilogue (one writer per element, an uncontended
+    add) unless ``slab1``; otherwise every split stores its fp32 slab to ``ws`` and
+    ``reduce(ws)`` (default: the flat splitk_reduce into dw) adds the slabs in fixed order."""
+    amode, M, N, K, splits, kstep = (plan[k] for k in ("amode", "M", "N", "K", "splits", "kstep"))
+    if splits == 1 and not slab1:
         if not accumulate:
             dw.zero_()
         gemm(A, B, dw, amode=amode, bmode=B_NC, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=N, epi=E_ATOMIC, geo=geo,
-             tile=t)
+             k_per_split=plan["kps"], tile=plan["tile"], kstep=kstep)
         return
-    need = splits * M * N
-    if workspace is None or workspace.numel() < need or workspace.dtype != torch.float32:
-        raise ValueError(f"weight-gradient GEMM needs an fp32 workspace of {need} elements")
-    gemm(A, B, workspace, amode=amode, bmode=B_NC, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=N, epi=E_SLAB,
-         splits=splits, k_per_split=kps, tile=t, geo=geo)
-    _C().splitk_reduce(_ptr(workspace), splits, M * N, _ptr(dw), stream_handle(), accumulate=int(accumulate))
+    gemm(A, B, ws, amode=amode, bmode=B_NC, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=N, epi=E_SLAB,
+         splits=splits, k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=kstep)
+    if reduce is not None:
+        reduce(ws)
+    else:
+        _C().splitk_reduce(_ptr(ws), splits, M * N, _ptr(dw), stream_handle(), accumulate=int(accumulate))
 
 
 def acc_reps(acc, C: int, words: int) -> int:
@@ -372,15 +354,10 @@ DENSE_SPLIT_TARGET_WG = int(os.environ.get("DAMD_DENSE_SPLIT_WG", "128"))  # 1: 
 
 def dense_split_plan(M: int, N: int, K: int) -> Tuple[int, int]:
     """(splits, k_per_split) of a dense forward / backprop-input GEMM [M,N] over K."""
-    t = pick_tile(N)
-    bm, bn = (256, 64) if t == 1 else (128, 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    kfull = -(-K // BK) * BK
+    tiles = tile_count(M, N, pick_tile(N))
     if tiles > DENSE_SPLIT_MAX_TILES or K < 2 * BK:
-        return 1, kfull
-    splits = max(1, min(-(-DENSE_SPLIT_TARGET_WG // tiles), K // BK))
-    kps = -(-(-(-K // splits)) // BK) * BK
-    return -(-K // kps), kps
+        return 1, -(-K // BK) * BK
+    return split_k(K, tiles, DENSE_SPLIT_TARGET_WG, BK, K // BK)
 
 
 def dense_workspace_elems(M: int, N: int, K: int) -> int:
@@ -450,9 +427,15 @@ def dense_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, workspace: 
     _chk(x, torch.bfloat16, "x")
     _chk(dy, torch.bfloat16, "dy")
     _chk(dw, torch.float32, "dw")
-    if workspace is None and wgrad_workspace_elems(K, N, M):
-        workspace = torch.empty(wgrad_workspace_elems(K, N, M), device=x.device)
-    _wgrad_gemm(x, dy, dw, workspace, amode=A_MC, M=K, N=N, K=M, lda=K, ldb=N, accumulate=accumulate)
+    plan = dense_wgrad_plan(K, N, M)
+    if workspace is None and plan["ws"]:
+        workspace = torch.empty(plan["ws"], device=x.device)
+    # (a caller's workspace too small for the one-slab route: the atomic epilogue instead)
+    slab1 = plan["slab1"] and workspace.numel() >= K * N
+    need = plan["splits"] * K * N
+    if (plan["splits"] > 1 or slab1) and (workspace.numel() < need or workspace.dtype != torch.float32):
+        raise ValueError(f"weight-gradient GEMM needs an fp32 workspace of {need} elements")
+    _wgrad_launch(x, dy, dw, workspace, plan, lda=K, ldb=N, accumulate=accumulate, slab1=slab1)
 
 
 # ---- conv ---------------------------------------------------------------------------------
@@ -497,20 +480,7 @@ def conv_fwd_stem4(x, w8, out, kernel_size, strides=(2, 2), padding="same", bias
     assert tuple(out.shape) == (n, ho, wo, cout)
     plan = conv_fwd_plan(x.shape, wshape, strides, padding)
     _check_stats(stats, plan, cout, "conv_fwd_stem4")
-    M, K = plan["M"], plan["K"]
-    geo = (h, wd, 4, ho, wo, kh, 8, s, pad)
-    if plan["splits"] == 1:
-        epi = (E_BIAS if bias is not None else 0) | (E_RELU if relu else 0) | E_BF16 | \
-            (E_STATS if stats is not None else 0)
-        gemm(x, w8, out, amode=A_CONV64, bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=epi, bias=bias,
-             stats=stats, geo=geo, tile=plan["tile"], kstep=32)
-        return
-    ws = _workspace(workspace, plan["ws"], x.device)
-    gemm(x, w8, ws, amode=A_CONV64, bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=E_SLAB,
-         splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=32)
-    sp, sa, reps = _stats_ptrs(stats, cout)
-    _C().splitk_finish(_ptr(ws), plan["splits"], M, cout, _ptr(bias), 0, int(relu), sp, FINISH_RB,
-                       _ptr(out), cout, stream_handle(), stats_acc=sa, stats_reps=reps)
+    _conv_fwd_launch(x, w8, out, plan, (h, wd, 4, ho, wo, kh, 8, s, pad), bias, relu, stats, workspace, kstep=32)
 
 
 def _check_stats(stats, plan, cout, who):
@@ -541,26 +511,19 @@ def conv_wgrad_stem4(x, dy, dw8, kernel_size, strides=(2, 2), padding="same",
     plan = conv_wgrad_plan(x.shape, wshape, strides, padding)
     n, h, wd, cin, ho, wo, kh, kw, s, pad, cout = conv_geo(x.shape, wshape, strides, padding)
     geo = (h, wd, 4, ho, wo, kh, 8, s, pad)
-    M, N, K, splits = plan["M"], plan["N"], plan["K"], plan["splits"]
-    if splits == 1:
-        if not accumulate:
-            dw8.zero_()
-        gemm(x, dy, dw8, amode=A_WGRAD64, bmode=B_NC, M=M, N=N, K=K, ldb=cout, ldc=N, epi=E_ATOMIC, geo=geo,
-             k_per_split=plan["kps"], tile=plan["tile"], kstep=plan["kstep"])
-        return False
-    workspace = _workspace(workspace, plan["ws"], x.device)
-    gemm(x, dy, workspace, amode=A_WGRAD64, bmode=B_NC, M=M, N=N, K=K, ldb=cout, ldc=N, epi=E_SLAB,
-         splits=splits, k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=plan["kstep"])
-    if dw is not None:
+    splits = plan["splits"]
+
+    def reduce_unpad(ws):  # the reduce's rows [KH][8][4 x Cout] -> [KH][KW][Cin x Cout]
         _chk(dw, torch.float32, "dw")
         ci = dw.shape[2] if dw.dim() == 4 else 0
         if tuple(dw.shape) != (k, k, ci, cout) or not 1 <= ci <= 4:
             raise ValueError(f"conv_wgrad_stem4: dw shape {tuple(dw.shape)} is not [{k}][{k}][<=4][{cout}]")
-        # the reduce's rows [KH][8][4 x Cout] -> [KH][KW][Cin x Cout]
-        _C().splitk_reduce_unpad(_ptr(workspace), splits, k, k, ci * cout, 8, 4 * cout, _ptr(dw), stream_handle(), 1)
-        return True
-    _C().splitk_reduce(_ptr(workspace), splits, M * N, _ptr(dw8), stream_handle(), accumulate=int(accumulate))
-    return False
+        _C().splitk_reduce_unpad(_ptr(ws), splits, k, k, ci * cout, 8, 4 * cout, _ptr(dw), stream_handle(), 1)
+
+    unpad = dw is not None and splits > 1
+    _wgrad_launch(x, dy, dw8, _workspace(workspace, plan["ws"], x.device), plan, ldb=cout, geo=geo,
+                  accumulate=accumulate, reduce=reduce_unpad if unpad else None)
+    return unpad
 
 
 # ---- direct 3x3 / stride-1 / pad-1 convolution (csrc/kernels/conv3x3.hip) ---------------
@@ -638,29 +601,32 @@ def conv_fwd(x, w, out, strides=(1, 1), padding="valid", bias=None, relu=False, 
         raise ValueError("conv_fwd: Cin and Cout must be multiples of 8 (pad the channels)")
     assert tuple(out.shape) == (n, ho, wo, cout)
     plan = conv_fwd_plan(x.shape, w.shape, strides, padding)
-    M, K = plan["M"], plan["K"]
     _check_stats(stats, plan, cout, "conv_fwd")
     geo = (h, wd, cin, ho, wo, kh, kw, s, pad)
     if bnin is not None and (plan["amode"] != A_CONV3 or plan["splits"] != 1 or bnin[0].acc is None
                              or tuple(bnin[1].shape) != tuple(x.shape)):
         raise ValueError("conv_fwd: a BN input needs a direct 3x3 plan and y of x's shape")
+    _conv_fwd_launch(x, w, out, plan, geo, bias, relu, stats, workspace, bnin=bnin, fixup=True)
+
+
+def _conv_fwd_launch(x, w, out, plan, geo, bias, relu, stats, workspace, *, kstep=0, bnin=None, fixup=False):
+    """The forward GEMM of ``plan``: the fused epilogue for one split, else fp32 slabs +
+    splitk_finish (``fixup``: finished inside the launch where splitk_fixup_on allows)."""
+    M, K, cout = plan["M"], plan["K"], plan["N"]
+    epi = (E_BIAS if bias is not None else 0) | (E_RELU if relu else 0) | E_BF16 | (E_STATS if stats is not None else 0)
     if plan["splits"] == 1:
-        epi = (E_BIAS if bias is not None else 0) | (E_RELU if relu else 0) | E_BF16 | \
-            (E_STATS if stats is not None else 0)
         gemm(x, w, out, amode=plan["amode"], bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=epi,
-             bias=bias, stats=stats, geo=geo, tile=plan["tile"], bnin=bnin)
+             bias=bias, stats=stats, geo=geo, tile=plan["tile"], kstep=kstep, bnin=bnin)
         return
     ws = _workspace(workspace, plan["ws"], x.device)
-    if plan["amode"] in (A_CONV64,) and splitk_fixup_on(stats) and cout % 4 == 0:
-        epi = E_FIXUP | (E_BIAS if bias is not None else 0) | (E_RELU if relu else 0) | E_BF16 | \
-            (E_STATS if stats is not None else 0)
-        if not (relu and stats is not None):  # (no kernel instantiates both)
-            gemm(x, w, out, amode=plan["amode"], bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=epi,
-                 bias=bias, stats=stats, splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo,
-                 slab=ws)
-            return
+    if fixup and plan["amode"] == A_CONV64 and splitk_fixup_on(stats) and cout % 4 == 0 \
+            and not (relu and stats is not None):  # (no kernel instantiates both)
+        gemm(x, w, out, amode=plan["amode"], bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=E_FIXUP | epi,
+             bias=bias, stats=stats, splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo,
+             slab=ws)
+        return
     gemm(x, w, ws, amode=plan["amode"], bmode=B_NC, M=M, N=cout, K=K, ldb=cout, ldc=cout, epi=E_SLAB,
-         splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo)
+         splits=plan["splits"], k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=kstep)
     sp, sa, reps = _stats_ptrs(stats, cout)
     _C().splitk_finish(_ptr(ws), plan["splits"], M, cout, _ptr(bias), 0, int(relu), sp, FINISH_RB,
                        _ptr(out), cout, stream_handle(), stats_acc=sa, stats_reps=reps)
@@ -760,18 +726,8 @@ def conv_wgrad(x, dy, dw, strides=(1, 1), padding="valid", workspace: Optional[t
     if cin % 8 or cout % 8:
         raise ValueError("conv_wgrad: Cin and Cout must be multiples of 8")
     plan = conv_wgrad_plan(x.shape, dw.shape, strides, padding)
-    M, N, K, splits = plan["M"], plan["N"], plan["K"], plan["splits"]
-    geo = (h, wd, cin, ho, wo, kh, kw, s, pad)
-    if splits == 1:  # one writer per element: the atomic epilogue is an uncontended add
-        if not accumulate:
-            dw.zero_()
-        gemm(x, dy, dw, amode=plan["amode"], bmode=B_NC, M=M, N=N, K=K, ldb=cout, ldc=N, epi=E_ATOMIC, geo=geo,
-             k_per_split=plan["kps"], tile=plan["tile"], kstep=plan["kstep"])
-        return
-    workspace = _workspace(workspace, plan["ws"], x.device)
-    gemm(x, dy, workspace, amode=plan["amode"], bmode=B_NC, M=M, N=N, K=K, ldb=cout, ldc=N, epi=E_SLAB,
-         splits=splits, k_per_split=plan["kps"], tile=plan["tile"], geo=geo, kstep=plan["kstep"])
-    _C().splitk_reduce(_ptr(workspace), splits, M * N, _ptr(dw), stream_handle(), accumulate=int(accumulate))
+    _wgrad_launch(x, dy, dw, _workspace(workspace, plan["ws"], x.device), plan, ldb=cout,
+                  geo=(h, wd, cin, ho, wo, kh, kw, s, pad), accumulate=accumulate)
 
 
 # ---- BN / pooling / loss / optimizer -------------------------------------------------------------

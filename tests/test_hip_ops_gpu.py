@@ -54,7 +54,7 @@ def test_dense_fwd(H, M, K, N, relu, bias, out_bf16):
     close(out, r, 1e-2 if out_bf16 else 1e-4, 4e-3 if out_bf16 else 1e-5)
 
 
-@pytest.mark.parametrize("M,K,N", [(64, 512, 1000), (64, 5408, 64), (37, 24, 40)])
+@pytest.mark.parametrize("M,K,N", [(64, 512, 1000), (64, 5408, 64), (37, 24, 40), (512, 24, 40)])
 def test_dense_backward(H, M, K, N):
     x = rb(rnd(M, K, seed=4))
     w = rb(rnd(K, N, scale=0.1, seed=5))
