@@ -12,7 +12,6 @@ class ExchangeFault(RuntimeError):
     snapshot on the next transport, instead of the whole gang restarting."""
 
 
-
 class Engine:
     """Executes training steps for one (model, strategy, batch) configuration."""
 
@@ -63,6 +62,13 @@ class Engine:
 
     def sync(self):
         pass
+
+    def _host_iterations(self) -> int:
+        """``optimizer.iterations`` as the host holds it (a restored checkpoint's), for an
+        engine whose ``_iterations`` answers from the device's counter from here on."""
+        opt = self.model.optimizer
+        opt._iter_source = self._iterations
+        return int(opt._iterations)
 
     def completion_event(self):
         """An event that completes when the work enqueued so far has finished on the device

@@ -32,8 +32,8 @@ def as_u8_over_255(x: np.ndarray):
 
 
 class DataFeed:
-    def __init__(self, x, y, device: torch.device, flatten: bool = False, label_dtype=torch.int32,
-                 allow_u8: bool = False, w=None):
+    def __init__(self, x, y, device: torch.device, flatten: bool = False, allow_u8: bool = False, w=None):
+        self._key = (id(x), id(y), len(x))  # what a later bind compares its arrays with (built_from)
         x = np.asarray(x)
         y = np.asarray(y)
         if len(x) != len(y):
@@ -48,7 +48,6 @@ class DataFeed:
             if self.w_host.shape[0] != self.n:
                 raise ValueError(f"x has {self.n} rows but there are {self.w_host.shape[0]} sample weights")
             self.w = torch.from_numpy(self.w_host).to(device)
-        self.sample_shape = tuple(x.shape[1:])
         u8 = as_u8_over_255(x) if allow_u8 else None
         self.x_u8 = u8 is not None
         xt = torch.from_numpy(np.ascontiguousarray(u8 if self.x_u8 else x, dtype=np.uint8 if self.x_u8 else np.float32))
@@ -57,13 +56,32 @@ class DataFeed:
         self.x = xt.to(device)
         if y.ndim > 1 and y.shape[-1] > 1:  # one-hot / dense targets
             self.y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(device)
-        elif np.issubdtype(y.dtype, np.integer) or label_dtype == torch.int32:
+        else:  # class ids
             self.y = torch.from_numpy(np.ascontiguousarray(y.reshape(self.n), dtype=np.int64)).to(device).to(
                 torch.int32)
-        else:
-            self.y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(device)
         self.perm = torch.arange(self.n, dtype=torch.int32, device=device)
         self.device = device
+
+    def built_from(self, x, y, w=None) -> bool:
+        """This feed was built from these very arrays (by identity and length; a native
+        engine passes ``x`` after its ``np.asarray``) and the same weights (by value)."""
+        return self._key == (id(x), id(y), len(x)) and self.same_weights(w)
+
+    def alloc_epoch(self) -> None:
+        """x, y (and the weights) in epoch order, for the engines that read batches at a device
+        cursor.  Once per feed: captured graphs and the fused trainer hold the addresses."""
+        self.x_ep = torch.empty_like(self.x)
+        self.y_ep = torch.empty_like(self.y)
+        self.w_ep = torch.empty_like(self.w) if self.w is not None else None
+
+    def fill_epoch(self) -> None:
+        """Materialise the order of the last ``set_epoch`` once (one gather per epoch instead
+        of an index indirection on every step's critical path)."""
+        perm = self.perm.long()
+        torch.index_select(self.x, 0, perm, out=self.x_ep)
+        torch.index_select(self.y, 0, perm, out=self.y_ep)
+        if self.w_ep is not None:
+            torch.index_select(self.w, 0, perm, out=self.w_ep)
 
     def same_weights(self, w) -> bool:
         """``w`` (None or an array) is what this feed was built with."""

@@ -14,14 +14,14 @@ trained values after ``finish()`` (which applies the last pending update).
 """
 from __future__ import annotations
 
-import struct
-
 import numpy as np
 import torch
 
 from ..utils import env
 from ..utils import logging as dlog
-from .base import Engine, ExchangeFault  # noqa: F401  (ExchangeFault: re-exported)
+from .base import Engine, ExchangeFault
+from .convnet_buffers import NCONV, NPARAM, OFF_B1, OFF_W1, SHAPES, ConvNetBuffers, exchange_capacity
+from .ctrl import C_BAD, C_GB, C_IT, C_LR, C_NS, C_ROW0, epoch_metrics, epoch_start_words, f2i, hparam_words, rmw
 from .data import DataFeed
 
 
@@ -29,14 +29,6 @@ class ExchangeSelfTestError(RuntimeError):
     """A pinned device gradient exchange (DAMD_ALLREDUCE=xgmi | sharded) failed its start-up
     self-test (engine/xchg_selftest.py).  Raised on EVERY rank (the outcome is a collective
     vote), so a caller may catch it and go on with another transport consistently."""
-
-NPARAM = 347146
-NGRAD = 347152
-HID, NCLS, FEAT, NCONV = 64, 10, 5408, 320
-# ctrl word indices (csrc/include/damd_common.h struct Ctrl)
-(C_LR, C_MOM, C_NEST, C_NS, C_ROW0, C_GB, C_CUR, C_IT, C_CA, C_CB, C_AL, C_AC, C_AN, C_WRAP, C_CUR2, C_CUR3, C_WPAR,
- C_FLUSHT, C_PEND, C_PAR2, C_BAD, C_XCNT, C_XCNT2, C_TICKET, C_PEND2, C_XGEN) = range(26)
-SHAPES = [(3, 3, 1, 32), (32,), (5408, 64), (64,), (64, 10), (10,)]
 
 
 def _xchg_fault_at(rank: int, world: int):
@@ -47,15 +39,7 @@ def _xchg_fault_at(rank: int, world: int):
     return int(st) if int(r) == rank else None
 
 
-def _f2i(f: float) -> int:
-    return struct.unpack("<i", struct.pack("<f", float(f)))[0]
-
-
-def _i2f(i: int) -> float:
-    return struct.unpack("<f", struct.pack("<i", int(i)))[0]
-
-
-class FusedConvNetEngine(Engine):
+class FusedConvNetEngine(Engine, ConvNetBuffers):
     name = "fused_convnet"
 
     @staticmethod
@@ -121,35 +105,9 @@ class FusedConvNetEngine(Engine):
         self.PPB = env.get_int("DAMD_PP_BWD", 2)
         if not 1 <= self.PPB <= 4:
             raise ValueError("DAMD_PP_BWD must be in [1, 4]")
-        NS = C.convnet_num_slices(self.PP)
-        f32 = dict(dtype=torch.float32, device=dev)
-        BP = (B + 63) // 64 * 64  # padded batch pitch of the feature-major buffers
-        self.P = torch.zeros(NGRAD, **f32)
-        self.G = torch.zeros(C.convnet_grad_count(self.PP), **f32)  # grads + metric tail
-        self.V = torch.zeros(NGRAD, **f32)
-        self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-        self.w1alt = torch.zeros(FEAT * HID, **f32)   # W1 double buffer (by step parity)
-        self.v1alt = torch.zeros(FEAT * HID, **f32)
-        # bf16 copy of W1, one buffer per step parity: a step reads the buffer of its parity,
-        # the eager update in bwd writes the other one (convnet.h); `w1bf` is the live one.
-        # Two allocations of 0.7 MB, not one of 1.4 MB: as one tensor (a request above 1 MB,
-        # which the caching allocator serves from other segments) the forward kernel measured
-        # 0.4 us longer; why was not established (BENCH.md, round 11)
-        self.w1bf_bufs = tuple(torch.zeros(FEAT * HID, dtype=torch.bfloat16, device=dev) for _ in range(2))
-        self.pooled = torch.zeros(FEAT, BP, dtype=torch.bfloat16, device=dev)
-        self.code = torch.zeros(B, FEAT, dtype=torch.uint8, device=dev)
-        self.hacc = torch.zeros(C.convnet_hacc_elems(B), dtype=torch.int64, device=dev)  # by step parity
-        self.hconv = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)
-        self.calt = torch.zeros(2 * NCONV, **f32)  # alternate conv parameters + velocity
-        # next-batch prefetch (B <= 64): bwd copies the next step's rows here for the next fwd,
-        # tagged with the ctrl block's data generation + cursor (DAMD_XPREFETCH=0: off)
-        self.xnext = self.xtag = self.xcur = self.ycur = None
-        if B <= 64 and env.get_bool("DAMD_XPREFETCH", True):
-            self.xnext = torch.zeros(B * 784, **f32)  # (u8 rows use the first quarter)
-            self.xtag = torch.zeros(1, dtype=torch.int64, device=dev)
-            # this step's rows / labels as the fwd read them, for the bwd (no cursor needed)
-            self.xcur = torch.zeros(B * 784, **f32)
-            self.ycur = torch.zeros(B, dtype=torch.int32, device=dev)
+        # the buffers are the engine's own attributes (next-batch prefetch: B <= 64; DAMD_XPREFETCH=0: off)
+        ConvNetBuffers.__init__(self, C, dev, B, self.PP, parity_w1bf=True,
+                                prefetch=B <= 64 and env.get_bool("DAMD_XPREFETCH", True))
         # model variables -> views of the fp32 master buffer (Keras weight order)
         self.vars = model.trainable_weights
         off = 0
@@ -161,165 +119,36 @@ class FusedConvNetEngine(Engine):
             off += n
         self._own_variables(self.vars)
         opt = model.optimizer
-        if opt.momentum and "momentum" in opt.slots and opt.slots["momentum"].numel() == NPARAM:
-            self.V[:NPARAM].copy_(opt.slots["momentum"].to(dev))
+        self._load_momentum()
         if self.world > 1:
             strategy.communicator.broadcast_(self.P, 0)  # mirrored variables start equal
-        c = self.ctrl.cpu()
-        c[C_IT] = int(opt.iterations)
-        self.ctrl.copy_(c.to(dev))
-        self._write_hparams()
+        rmw(self.ctrl, {C_IT: int(opt.iterations), C_ROW0: self.rank * B, C_GB: global_batch})
+        rmw(self.ctrl, hparam_words(opt.learning_rate, opt.momentum, opt.nesterov))
         torch.cuda.synchronize(dev)
-        bufs = dict(params=self.P.data_ptr(), grads=self.G.data_ptr(), velocity=self.V.data_ptr(),
-                    ctrl=self.ctrl.data_ptr(),
-                    pooled=self.pooled.data_ptr(), code=self.code.data_ptr(), w1alt=self.w1alt.data_ptr(),
-                    v1alt=self.v1alt.data_ptr(), w1bf=self.w1bf_bufs[0].data_ptr(),
-                    w1bf_alt=self.w1bf_bufs[1].data_ptr(),
-                    hacc=self.hacc.data_ptr(), hconv=self.hconv.data_ptr(), calt=self.calt.data_ptr(),
-                    ppb=self.PPB)
-        if self.xnext is not None:
-            bufs.update(xnext=self.xnext.data_ptr(), xtag=self.xtag.data_ptr(), xcur=self.xcur.data_ptr(),
-                        ycur=self.ycur.data_ptr())
         # world 1 (no gradient all-reduce): bwd applies the W1 update itself as soon as it
         # has the slice's gradient, and fwd reads only the bf16 copy (DAMD_EAGER_W1=0: the
         # deferred update in fwd, as with an all-reduce between the launches)
-        force_ar = env.get_bool("DAMD_FORCE_ALLREDUCE", False)
-        # (B <= 64: the single-chunk backward; the multi-chunk one has no registers to spare
-        # for the slice's masters)
-        self.eager_w1 = self.world == 1 and not force_ar and B <= 64 and env.get_bool("DAMD_EAGER_W1", True)
-        bufs["eager_w1"] = int(self.eager_w1)
-        # the flagship configuration (world 1, 64 images, default slicing, eager update) has
-        # step kernels compiled for exactly its sizes; DAMD_SPECIALISED=0 runs the generic
-        # (runtime-size) kernels there too -- same results bit for bit, for A/B runs
-        bufs["specialised"] = int(env.get_bool("DAMD_SPECIALISED", True))
-        self.stamps = None
-        if env.get_bool("DAMD_STAMPS", False):  # diagnostics: per-phase s_memrealtime stamps
-            self.stamps = torch.zeros(3, 256, 16, dtype=torch.int64, device=dev)
-            bufs["stamps"] = self.stamps.data_ptr()
-        self.trainer = C.ConvNetTrainer(dev.index or 0, bufs, B, self.PP, 1)
-        self._refresh_w1bf()
         # DAMD_FORCE_ALLREDUCE=1 keeps the (size-1) RCCL all-reduce inside the captured step
         # at world 1: the multi-GPU graph path exercised on a single GPU
         force = env.get_bool("DAMD_FORCE_ALLREDUCE", False)
+        # (B <= 64: the single-chunk backward; the multi-chunk one has no registers to spare
+        # for the slice's masters)
+        self.eager_w1 = self.world == 1 and not force and B <= 64 and env.get_bool("DAMD_EAGER_W1", True)
+        # the flagship configuration (world 1, 64 images, default slicing, eager update) has
+        # step kernels compiled for exactly its sizes; DAMD_SPECIALISED=0 runs the generic
+        # (runtime-size) kernels there too -- same results bit for bit, for A/B runs
+        if env.get_bool("DAMD_STAMPS", False):  # diagnostics: per-phase s_memrealtime stamps
+            self.stamps = torch.zeros(3, 256, 16, dtype=torch.int64, device=dev)
+        bufs = self.trainer_args(self.PPB, eager_w1=self.eager_w1, specialised=env.get_bool("DAMD_SPECIALISED", True))
+        self.trainer = C.ConvNetTrainer(dev.index or 0, bufs, B, self.PP, 1)
+        self._refresh_w1bf()
         native = strategy.communicator.native if (self.world > 1 or force) else None
-        if "rccl" in (exclude or ()):
-            native = None  # RCCL faulted mid-run on this gang: host all-reduce from here on
-        # per-step gradient exchange at world > 1 (DAMD_ALLREDUCE):
-        #   auto / sharded -- inside the two step kernels (convnet.h XArgs): each rank owns a
-        #       quarter-slice unit of dW1 per 1/world of the units, bwd pushes partials to the
-        #       owners over xGMI, owners reduce in rank order and push the reduced units back;
-        #       the small gradients + metrics travel as one message per rank.  No extra launch.
-        #   xgmi -- the standalone two-shot peer all-reduce kernel after bwd (folded staging)
-        #   rccl -- RCCL inside the captured step; off -- no device transport (RCCL if the
-        #       communicator has one, else the host-staged gloo all-reduce between steps)
-        # Both peer modes need every rank to map every peer (one node); else RCCL.
-        self.peer = None
-        self.sharded = False
         # transports never to use again on this engine: the ones a mid-run exchange fault
         # was detected on (rebuild_after_fault)
         self.exclude = set(exclude or ())
-        self.transport_us: dict = {}  # measured us / step per candidate exchange (auto mode)
-        # start-up self-test outcome of the device exchange (None: no device exchange was
-        # self-tested -- world 1, RCCL or the host all-reduce) and the transports that failed it
-        self.exchange_verified = None
-        self.exchange_fallback_from: list = []
-        self.hred = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)  # sharded: conv sums for flush
-        mode = env.get_str("DAMD_ALLREDUCE", "auto").lower()
-        self._mode = mode
-        if mode not in ("auto", "sharded", "xgmi", "rccl", "off"):
-            raise ValueError("DAMD_ALLREDUCE must be auto, sharded, xgmi, rccl or off")
-        # DAMD_GRAD_DTYPE=bf16: the exchanged dW1 travels as bf16 (fp32 accumulation by the
-        # owner, fp32 master update); default fp32 (reference parity)
-        self.grad_dtype = env.get_str("DAMD_GRAD_DTYPE", "fp32").lower()
-        if self.grad_dtype not in ("fp32", "bf16"):
-            raise ValueError("DAMD_GRAD_DTYPE must be fp32 or bf16")
-        if self.world > 1 and mode not in ("rccl", "off") and not {"xgmi-sharded", "xgmi-peer"} <= self.exclude:
-            from ..parallel.communicator import make_peer_allreduce
-
-            # in-kernel wait deadline: the collective watchdog's (its default included), so a
-            # missing peer is reported by the kernel's status word no later than the watchdog
-            from ..utils.watchdog import deadline_for
-
-            wd = deadline_for(self.world)
-            want_sharded = mode in ("auto", "sharded") and self.world <= 8
-            if want_sharded:
-                NU = 4 * C.convnet_num_slices(self.PPB)
-                cap = max(self.world * NU * 2048, 347648 + 2 * 8 * 1408 + 16384 + FEAT * HID // 2)
-            else:
-                cap = C.PeerAllreduce.message_words(C.convnet_grad_count(self.PP), 2 * NCONV)
-            self.peer = make_peer_allreduce(strategy.communicator, dev.index or 0, cap,
-                                            blocks=env.get_int("DAMD_PEER_BLOCKS", 64),
-                                            timeout_s=wd if wd > 0 else 60.0)
-            if self.peer is None and mode in ("xgmi", "sharded"):
-                raise RuntimeError(f"DAMD_ALLREDUCE={mode} but the xGMI peer mapping is unavailable")
-            if self.peer is not None:
-                # ranks sharing one device (the 1-GPU rehearsal of a multi-GPU run): each
-                # rank's step stream gets its own CUs -- the in-kernel waits of one rank must
-                # not hold the CUs another rank needs to publish what they wait for
-                # (two ranks need no split: one rank's waiting forward leaves the other's
-                # 57-169-block backward enough CUs to finish -- measured 44.7 us/step shared
-                # vs 78 us with halved CUs; from three ranks on, the waiting forwards of two
-                # ranks can hold every CU)
-                ndev = max(1, torch.cuda.device_count())
-                share = [q for q in range(self.world) if q % ndev == (dev.index or 0)]
-                cu_split = ((share.index(self.rank), len(share))
-                            if len(share) > 2 and env.get_bool("DAMD_SHARED_CU_SPLIT", True) else None)
-                # start-up self-test of each candidate transport against the host rank-order
-                # reduction, bitwise, on every rank (engine/xchg_selftest.py); then, with the
-                # transport not pinned, every candidate that passed (and RCCL) is TIMED the way
-                # bench.py times its window, and the fastest carries the run (reference
-                # README.md:398, communication = AUTO).  Without tuning: the first that passes,
-                # sharded -> xgmi -> RCCL.
-                cands = [k for k in ((["xgmi-sharded"] if want_sharded else [])
-                                     + ([] if mode == "sharded" else ["xgmi-peer"])) if k not in self.exclude]
-                tune = (mode == "auto" and env.get_bool("DAMD_XCHG_TUNE", True))
-                from . import xchg_selftest
-
-                passed = []
-                selftested = env.get_bool("DAMD_XCHG_SELFTEST", True)
-                if selftested:
-                    for kind in cands:
-                        if xchg_selftest.verify(kind, C, strategy.communicator, self.peer, dev, B, self.PPB, self.PP,
-                                                self.P, gbf16=self.grad_dtype == "bf16" and kind == "xgmi-sharded",
-                                                cu_split=cu_split):
-                            passed.append(kind)
-                            if not tune:
-                                break
-                        else:
-                            self.exchange_fallback_from.append(kind)
-                else:
-                    passed = list(cands) if tune else cands[:1]
-                chosen = passed[0] if passed else None
-                timed = passed + (["rccl"] if (native is not None and "rccl" not in self.exclude) else [])
-                if tune and len(timed) > 1:
-                    for kind in timed:
-                        t = xchg_selftest.time_transport(kind, C, strategy.communicator, self.peer, native, dev, B,
-                                                         self.PPB, self.PP, self.P,
-                                                         gbf16=self.grad_dtype == "bf16" and kind == "xgmi-sharded",
-                                                         cu_split=cu_split)
-                        if t is not None:
-                            self.transport_us[kind] = round(t * 1e6, 2)
-                    if self.transport_us:
-                        chosen = min(self.transport_us, key=self.transport_us.get)
-                # in-kernel wait deadline of the run (DAMD_XCHG_TIMEOUT_S: shorter, for tests)
-                self.peer.set_timeout(env.get_float("DAMD_XCHG_TIMEOUT_S", wd if wd > 0 else 60.0))
-                if selftested and chosen is not None and chosen != "rccl":
-                    self.exchange_verified = True
-                if chosen == "rccl":
-                    self.peer = None  # RCCL measured fastest: set_comm below
-                elif chosen is None:
-                    if mode in ("xgmi", "sharded"):
-                        raise ExchangeSelfTestError(f"DAMD_ALLREDUCE={mode}: the exchange failed its start-up self-test")
-                    dlog.warning("fused ConvNet engine: no xGMI exchange passed its self-test; using %s",
-                                 "RCCL" if native is not None else "the host (gloo) all-reduce")
-                    self.peer = None
-                elif chosen == "xgmi-sharded":
-                    self.trainer.set_sharded(self.peer, self.hred.data_ptr(), int(self.grad_dtype == "bf16"))
-                    self.sharded = True
-                    if cu_split is not None:
-                        self.trainer.restrict_cus(*cu_split)
-                    # every rank's flags are zero before any rank's first step writes into them
-                    strategy.communicator.barrier()
+        if "rccl" in self.exclude:
+            native = None  # RCCL faulted mid-run on this gang: host all-reduce from here on
+        self._init_exchange(C, native)
         if self.grad_dtype == "bf16" and not self.sharded:
             if self.world > 1:
                 dlog.warning("DAMD_GRAD_DTYPE=bf16 applies to the sharded exchange only; exchanging fp32")
@@ -354,7 +183,87 @@ class FusedConvNetEngine(Engine):
         self._pending = False
         self.steps_done = 0
         self._fault_done = bool(exclude)  # the fault injection fires once per gang
-        dlog.debug("fused ConvNet engine: B=%d, slices=%d, graph=%s", B, NS, self.use_graph)
+        dlog.debug("fused ConvNet engine: B=%d, slices=%d, graph=%s", B, C.convnet_num_slices(self.PP), self.use_graph)
+
+    def _init_exchange(self, C, native):
+        """The per-step gradient exchange at world > 1 (DAMD_ALLREDUCE):
+          auto / sharded -- inside the two step kernels (convnet.h XArgs): each rank owns a
+              quarter-slice unit of dW1 per 1/world of the units, bwd pushes partials to the
+              owners over xGMI, owners reduce in rank order and push the reduced units back;
+              the small gradients + metrics travel as one message per rank.  No extra launch.
+          xgmi -- the standalone two-shot peer all-reduce kernel after bwd (folded staging)
+          rccl -- RCCL inside the captured step; off -- no device transport (RCCL if the
+              communicator has one, else the host-staged gloo all-reduce between steps)
+        Both peer modes need every rank to map every peer (one node); else RCCL.  Leaves
+        ``peer`` (None: RCCL ``native`` or the host all-reduce) and ``sharded``."""
+        self.peer = None
+        self.sharded = False
+        self.transport_us: dict = {}  # measured us / step per candidate exchange (auto mode)
+        # start-up self-test outcome of the device exchange (None: no device exchange was
+        # self-tested -- world 1, RCCL or the host all-reduce) and the transports that failed it
+        self.exchange_verified = None
+        self.exchange_fallback_from: list = []
+        self.hred = torch.zeros(2 * NCONV, dtype=torch.int64, device=self.device)  # sharded: conv sums for flush
+        self._mode = mode = env.get_str("DAMD_ALLREDUCE", "auto").lower()
+        if mode not in ("auto", "sharded", "xgmi", "rccl", "off"):
+            raise ValueError("DAMD_ALLREDUCE must be auto, sharded, xgmi, rccl or off")
+        # DAMD_GRAD_DTYPE=bf16: the exchanged dW1 travels as bf16 (fp32 accumulation by the
+        # owner, fp32 master update); default fp32 (reference parity)
+        self.grad_dtype = env.get_str("DAMD_GRAD_DTYPE", "fp32").lower()
+        if self.grad_dtype not in ("fp32", "bf16"):
+            raise ValueError("DAMD_GRAD_DTYPE must be fp32 or bf16")
+        if self.world == 1 or mode in ("rccl", "off") or {"xgmi-sharded", "xgmi-peer"} <= self.exclude:
+            return
+        from ..parallel.communicator import make_peer_allreduce
+        # in-kernel wait deadline: the collective watchdog's (its default included), so a
+        # missing peer is reported by the kernel's status word no later than the watchdog
+        from ..utils.watchdog import deadline_for
+        from . import xchg_selftest
+
+        comm, dev, B = self.strategy.communicator, self.device, self.per_replica
+        wd = deadline_for(self.world)
+        wd = wd if wd > 0 else 60.0
+        cap = exchange_capacity(C, self.world, self.PP, self.PPB, mode in ("auto", "sharded") and self.world <= 8)
+        self.peer = make_peer_allreduce(comm, dev.index or 0, cap, blocks=env.get_int("DAMD_PEER_BLOCKS", 64),
+                                        timeout_s=wd)
+        if self.peer is None:
+            if mode in ("xgmi", "sharded"):
+                raise RuntimeError(f"DAMD_ALLREDUCE={mode} but the xGMI peer mapping is unavailable")
+            return
+        # ranks sharing one device (the 1-GPU rehearsal of a multi-GPU run): each rank's step stream gets
+        # its own CUs -- the in-kernel waits of one rank must not hold the CUs another rank needs to
+        # publish what they wait for (two ranks need no split: one rank's waiting forward leaves the
+        # other's 57-169-block backward enough CUs to finish -- measured 44.7 us/step shared vs 78 us with
+        # halved CUs; from three ranks on, the waiting forwards of two ranks can hold every CU)
+        ndev = max(1, torch.cuda.device_count())
+        share = [q for q in range(self.world) if q % ndev == (dev.index or 0)]
+        cu_split = ((share.index(self.rank), len(share))
+                    if len(share) > 2 and env.get_bool("DAMD_SHARED_CU_SPLIT", True) else None)
+        def args(kind):  # of the scratch trainers of the self-test and of the timing
+            return dev, B, self.PPB, self.PP, self.P, self.grad_dtype == "bf16" and kind == "xgmi-sharded", cu_split
+
+        chosen, self.exchange_verified, self.exchange_fallback_from, self.transport_us = xchg_selftest.choose_exchange(
+            mode, self.world, self.exclude, native is not None, env.get_bool("DAMD_XCHG_SELFTEST", True),
+            env.get_bool("DAMD_XCHG_TUNE", True),
+            verify=lambda kind: xchg_selftest.verify(kind, C, comm, self.peer, *args(kind)),
+            time=lambda kind: xchg_selftest.time_transport(kind, C, comm, self.peer, native, *args(kind)))
+        # in-kernel wait deadline of the run (DAMD_XCHG_TIMEOUT_S: shorter, for tests)
+        self.peer.set_timeout(env.get_float("DAMD_XCHG_TIMEOUT_S", wd))
+        if chosen == "rccl":
+            self.peer = None  # RCCL measured fastest: set_comm in __init__
+        elif chosen is None:
+            if mode in ("xgmi", "sharded"):
+                raise ExchangeSelfTestError(f"DAMD_ALLREDUCE={mode}: the exchange failed its start-up self-test")
+            dlog.warning("fused ConvNet engine: no xGMI exchange passed its self-test; using %s",
+                         "RCCL" if native is not None else "the host (gloo) all-reduce")
+            self.peer = None
+        elif chosen == "xgmi-sharded":
+            self.trainer.set_sharded(self.peer, self.hred.data_ptr(), int(self.grad_dtype == "bf16"))
+            self.sharded = True
+            if cu_split is not None:
+                self.trainer.restrict_cus(*cu_split)
+            # every rank's flags are zero before any rank's first step writes into them
+            comm.barrier()
 
     @property
     def step_kernels(self) -> str:
@@ -383,24 +292,15 @@ class FusedConvNetEngine(Engine):
     def _ctrl_write(self, updates: dict):
         self.trainer.sync(self.watchdog_s) or self._watchdog_fired()
         self._check_peer()
-        c = self.ctrl.cpu()
-        for k, v in updates.items():
-            c[k] = v
         # any host write may move the cursor or follow new epoch rows: a batch the last bwd
         # prefetched must not match its tag any more
-        c[C_XGEN] = (int(c[C_XGEN]) + 1) & 0x7fffffff
-        self.ctrl.copy_(c.to(self.device))
+        rmw(self.ctrl, updates, bump_xgen=True)
         torch.cuda.synchronize(self.device)
 
-    def _write_hparams(self):
+    def _load_momentum(self):
         opt = self.model.optimizer
-        c = self.ctrl.cpu()
-        c[C_LR] = _f2i(opt.learning_rate)
-        c[C_MOM] = _f2i(opt.momentum)
-        c[C_NEST] = int(opt.nesterov)
-        c[C_ROW0] = self.rank * self.per_replica
-        c[C_GB] = self.global_batch
-        self.ctrl.copy_(c.to(self.device))
+        if opt.momentum and "momentum" in opt.slots and opt.slots["momentum"].numel() == NPARAM:
+            self.V[:NPARAM].copy_(opt.slots["momentum"].to(self.device))
 
     def _watchdog_fired(self):
         what = ("xGMI peer all-reduce wedged" if self.peer is not None else "RCCL communicator aborted")
@@ -412,18 +312,12 @@ class FusedConvNetEngine(Engine):
     def reload_optimizer_state(self):
         self._flush()
         self.trainer.sync(0.0)
-        opt = self.model.optimizer
-        if opt.momentum and "momentum" in opt.slots and opt.slots["momentum"].numel() == NPARAM:
-            self.V[:NPARAM].copy_(opt.slots["momentum"].to(self.device))
-        opt._iter_source = None
-        it = int(opt.iterations)
-        opt._iter_source = self._iterations
-        self._ctrl_write({C_IT: it})
+        self._load_momentum()
+        self._ctrl_write({C_IT: self._host_iterations()})
 
     def lr_changed(self):
         self._flush()
-        c = {C_LR: _f2i(self.model.optimizer.learning_rate)}
-        self._ctrl_write(c)
+        self._ctrl_write({C_LR: f2i(self.model.optimizer.learning_rate)})
 
     # --- data / epochs ---------------------------------------------------------------
     def bind(self, x, y, w=None):
@@ -432,19 +326,16 @@ class FusedConvNetEngine(Engine):
         x = np.asarray(x)
         if tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28), (784,)):
             raise ValueError(f"fused ConvNet engine expects 28x28x1 inputs, got {x.shape[1:]}")
-        key = (id(x), id(y), len(x))
-        if self.feed is None or getattr(self, "_feed_key", None) != key:
+        if self.feed is None or not self.feed.built_from(x, y):
             self.trainer.sync(0.0)
             self.feed = DataFeed(x, y, self.device, flatten=True, allow_u8=env.get_bool("DAMD_X_U8", True))
             if self.feed.n * 784 * (1 if self.feed.x_u8 else 4) >= 2 ** 31:
                 # the step kernels address the (epoch-permuted) dataset with 32-bit offsets
                 raise ValueError(f"fused ConvNet engine: {self.feed.n} rows exceed the 2 GiB dataset limit")
-            self._feed_key = key
             torch.cuda.synchronize(self.device)
-            self.x_ep = torch.empty_like(self.feed.x)
-            self.y_ep = torch.empty_like(self.feed.y)
+            self.feed.alloc_epoch()
             torch.cuda.synchronize(self.device)
-            self.trainer.set_data(self.x_ep.data_ptr(), self.y_ep.data_ptr(), int(self.feed.x_u8))
+            self.trainer.set_data(self.feed.x_ep.data_ptr(), self.feed.y_ep.data_ptr(), int(self.feed.x_u8))
             self._ctrl_write({C_NS: self.feed.n})
         return self.feed
 
@@ -454,14 +345,10 @@ class FusedConvNetEngine(Engine):
         self._flush()
         self.trainer.sync(0.0)
         self.feed.set_epoch(epoch, shuffle, self.shuffle_seed)
-        # materialise the epoch order once (one gather per epoch instead of an index
-        # indirection on every step's critical path)
-        perm = self.feed.perm.long()
-        torch.index_select(self.feed.x, 0, perm, out=self.x_ep)
-        torch.index_select(self.feed.y, 0, perm, out=self.y_ep)
+        self.feed.fill_epoch()
         opt = self.model.optimizer
-        self._ctrl_write({C_CUR: 0, C_AL: 0, C_AC: 0, C_AN: 0, C_WRAP: int(wrap_steps),
-                          C_LR: _f2i(opt.learning_rate), C_MOM: _f2i(opt.momentum), C_NEST: int(opt.nesterov)})
+        self._ctrl_write({**epoch_start_words(wrap_steps),
+                          **hparam_words(opt.learning_rate, opt.momentum, opt.nesterov)})
 
     def run(self, n_steps):
         fa = _xchg_fault_at(self.rank, self.world)
@@ -488,8 +375,7 @@ class FusedConvNetEngine(Engine):
             self._pending = True
             self.steps_done += n_steps
             return
-        if self.use_graph and n_steps >= self.graph_steps:
-            self.trainer.capture(self.graph_steps)
+        self.prepare(n_steps)
         if self.use_graph:
             self.trainer.run(n_steps)
         else:
@@ -562,16 +448,7 @@ class FusedConvNetEngine(Engine):
         # metric_tail's gather waits (bounded) for every rank's last message: a wait that
         # expired there leaves a stale tail -- never report it
         self._check_peer(soft)
-        loss = _i2f(c[C_AL]) + tail[0]
-        corr = _i2f(c[C_AC]) + tail[1]
-        cnt = _i2f(c[C_AN]) + tail[2]
-        d = max(cnt, 1.0)
-        # a non-finite / out-of-range value met a fixed-point sum (ctrl.bad): NaN, like the
-        # fp32 engines would show it (TerminateOnNaN must fire)
-        out = {"loss": float("nan") if c[C_BAD] else loss / d, "_count": cnt}
-        for m in self.model.compiled_metrics:
-            out[m.name] = corr / d
-        return out
+        return epoch_metrics(c, [m.name for m in self.model.compiled_metrics], tail=tail, check_bad=True)
 
     def end_epoch(self):
         self._flush()
@@ -632,9 +509,7 @@ class FusedConvNetEngine(Engine):
         return new
 
     def finish(self):
-        self._flush()
-        self.trainer.sync(self.watchdog_s) or self._watchdog_fired()
-        self._check_peer()  # never hand out weights built from a timed-out (partial) reduction
+        self.sync()
         opt = self.model.optimizer
         if opt.momentum:
             opt.ensure_slots(NPARAM, self.device)
@@ -651,7 +526,7 @@ class FusedConvNetEngine(Engine):
         both parity buffers, so whichever the next forward reads is current."""
         torch.cuda.synchronize(self.device)
         for buf in self.w1bf_bufs:
-            buf.copy_(self.P[NCONV:NCONV + FEAT * HID])
+            buf.copy_(self.P[OFF_W1:OFF_B1])
         torch.cuda.synchronize(self.device)
 
     def after_external_write(self):

@@ -143,10 +143,8 @@ class GenericEngine(Engine):
         self.bucket_of = {i: b for b, (_, _, idxs) in enumerate(self.buckets) for i in idxs}
 
     def bind(self, x, y, w=None):
-        key = (id(x), id(y), len(x))
-        if self.feed is None or getattr(self, "_feed_key", None) != key or not self.feed.same_weights(w):
+        if self.feed is None or not self.feed.built_from(x, y, w):
             self.feed = DataFeed(x, y, self.device, w=w)
-            self._feed_key = key
         return self.feed
 
     def start_epoch(self, epoch, shuffle):

@@ -28,7 +28,6 @@ the step (loss, backward ops, optimizer) and the driver.
 """
 from __future__ import annotations
 
-import struct
 import weakref
 from contextlib import contextmanager
 
@@ -39,6 +38,7 @@ from ..ops import hip as H
 from ..utils import env
 from ..utils import logging as dlog
 from .base import Engine
+from .ctrl import C_GB, C_IT, C_LR, C_NS, C_ROW0, epoch_metrics, epoch_start_words, f2i, hparam_words, rmw
 from .data import DataFeed
 from .native_buckets import BucketReducer
 from .native_exec import PlanExec, capture
@@ -46,18 +46,6 @@ from .native_params import FlatParams
 from .native_plan import (T, _act_name, _layer_graph, _opt_kernel_slots, _param_weights, _schedule_of, clipping_ok,
                           dense_targets, layers_eligible, loss_head_ok, lower, output_head, regularizers_ok,
                           schedule_ok)
-
-C_LR, C_MOM, C_NEST, C_NS, C_ROW0, C_GB, C_CUR, C_IT = 0, 1, 2, 3, 4, 5, 6, 7
-C_AL, C_AC, C_AN, C_WRAP = 10, 11, 12, 13
-
-
-def _f2i(f):
-    return struct.unpack("<i", struct.pack("<f", float(f)))[0]
-
-
-def _i2f(i):
-    return struct.unpack("<f", struct.pack("<i", int(i)))[0]
-
 
 class NativeGraphEngine(Engine):
     name = "native_graph"
@@ -122,9 +110,8 @@ class NativeGraphEngine(Engine):
         self._wgrad_side_minc = env.get_int("DAMD_WGRAD_STREAM_MINC", 0)  # convs with fewer outputs stay inline
         # ctrl
         self.ctrl = ex.ctrl
-        self._ctrl_write({C_IT: int(opt.iterations), C_LR: _f2i(self._host_lr()), C_ROW0: self.rank * self.per_replica,
-                          C_MOM: _f2i(getattr(opt, "momentum", 0.0)), C_NEST: int(getattr(opt, "nesterov", False)),
-                          C_GB: self.global_batch})
+        self._ctrl_write({C_IT: int(opt.iterations), C_ROW0: self.rank * self.per_replica, C_GB: self.global_batch,
+                          **self._hparam_words()})
         opt._iter_source = self._iterations
         self.graph = None
         self._phase_events = None  # phase_times(): (name, event) marks of an eager step
@@ -221,12 +208,13 @@ class NativeGraphEngine(Engine):
             return float(self.lr_sched(int(opt.iterations)))
         return opt.learning_rate
 
+    def _hparam_words(self):
+        opt = self.model.optimizer
+        return hparam_words(self._host_lr(), getattr(opt, "momentum", 0.0), getattr(opt, "nesterov", False))
+
     def _ctrl_write(self, updates):
         torch.cuda.synchronize(self.device)
-        c = self.ctrl.cpu()
-        for k, v in updates.items():
-            c[k] = v
-        self.ctrl.copy_(c.to(self.device))
+        rmw(self.ctrl, updates)
         torch.cuda.synchronize(self.device)
 
     def _iterations(self):
@@ -246,7 +234,7 @@ class NativeGraphEngine(Engine):
                 self.model._engine_key = None
                 return
             self._build_lr_table()
-        self._ctrl_write({C_LR: _f2i(self._host_lr())})
+        self._ctrl_write({C_LR: f2i(self._host_lr())})
 
     def _load_momentum(self):
         # optimizer slots are dense over the unpadded weights (Keras order)
@@ -261,12 +249,9 @@ class NativeGraphEngine(Engine):
                     o += sz
 
     def reload_optimizer_state(self):
-        opt = self.model.optimizer
         torch.cuda.synchronize(self.device)
         self._load_momentum()
-        opt._iter_source = None
-        it = int(opt.iterations)
-        opt._iter_source = self._iterations
+        it = self._host_iterations()
         H.cast_bf16(self.P, self.Pb)
         self._ctrl_write({C_IT: it})
 
@@ -283,19 +268,15 @@ class NativeGraphEngine(Engine):
                 raise ValueError(f"{type(self.model.loss).__name__} takes one-hot / dense targets of shape "
                                  f"(n, {self.K}) for this model, got y of shape {tuple(ys)}"
                                  " (to_categorical(y), or the sparse loss for class ids)")
-        key = (id(x), id(y), len(x))
-        if self.feed is None or getattr(self, "_feed_key", None) != key or not self.feed.same_weights(sw):
+        if self.feed is None or not self.feed.built_from(x, y, sw):
             torch.cuda.synchronize(self.device)
             self.feed = DataFeed(x, y, self.device, flatten=True, allow_u8=env.get_bool("DAMD_X_U8", True), w=sw)
             if self.dense_y and (self.feed.y.dtype != torch.float32 or tuple(self.feed.y.shape) !=
                                  (self.feed.n, self.K)):
                 raise ValueError(f"dense targets must be (n, {self.K}) numbers, got {tuple(self.feed.y.shape)}")
-            self._feed_key = key
-            self.x_ep = torch.empty_like(self.feed.x)
-            self.y_ep = torch.empty_like(self.feed.y)
-            # the weights in epoch order beside x_ep / y_ep: the loss launch reads the row at
-            # the device cursor (None: the unweighted launch)
-            self.w_ep = torch.empty_like(self.feed.w) if self.feed.w is not None else None
+            # (the weights in epoch order beside x_ep / y_ep: the loss launch reads the row at
+            # the device cursor; None: the unweighted launch)
+            self.feed.alloc_epoch()
             self.y_zero = torch.zeros(self.feed.n, dtype=torch.int32, device=self.device) if self.dense_y else None
             self.graph = None  # data pointers changed
             self._ctrl_write({C_NS: self.feed.n})
@@ -304,15 +285,8 @@ class NativeGraphEngine(Engine):
     def start_epoch(self, epoch, shuffle, wrap_steps: int = 0):
         torch.cuda.synchronize(self.device)
         self.feed.set_epoch(epoch, shuffle, self.shuffle_seed)
-        perm = self.feed.perm.long()
-        torch.index_select(self.feed.x, 0, perm, out=self.x_ep)
-        torch.index_select(self.feed.y, 0, perm, out=self.y_ep)
-        if self.w_ep is not None:
-            torch.index_select(self.feed.w, 0, perm, out=self.w_ep)
-        opt = self.model.optimizer
-        self._ctrl_write({C_CUR: 0, C_AL: 0, C_AC: 0, C_AN: 0, C_WRAP: int(wrap_steps),
-                          C_LR: _f2i(self._host_lr()), C_MOM: _f2i(getattr(opt, "momentum", 0.0)),
-                          C_NEST: int(getattr(opt, "nesterov", False))})
+        self.feed.fill_epoch()
+        self._ctrl_write({**epoch_start_words(wrap_steps), **self._hparam_words()})
 
     # --- the step ----------------------------------------------------------------------------
     def _mark(self, name):
@@ -335,8 +309,9 @@ class NativeGraphEngine(Engine):
         job = ex.pad_job(ex.pad_folded) if ex.pad_folded is not None else None
         # (dense targets: gather_batch gets an all-zero label array, so self.labels still
         # carries 0 for a real row and -1 for one past the end of the data)
-        y_ids = self.y_zero if self.dense_y else self.y_ep
-        C.gather_batch(self.x_ep.data_ptr(), int(self.feed.x_u8), 255.0, y_ids.data_ptr(), self.ctrl.data_ptr(),
+        feed = self.feed
+        y_ids = self.y_zero if self.dense_y else feed.y_ep
+        C.gather_batch(feed.x_ep.data_ptr(), int(feed.x_u8), 255.0, y_ids.data_ptr(), self.ctrl.data_ptr(),
                        B, h * w, c, self.cin_pad, self.x0.buf.data_ptr(), self.labels.data_ptr(), s,
                        zero=self.G.data_ptr(), zero_bytes=self.G.numel() * 4,
                        zero2=acc.data_ptr() if acc is not None else 0, zero2_bytes=acc.numel() * 8 if acc is not None else 0,
@@ -349,13 +324,13 @@ class NativeGraphEngine(Engine):
         if self.dense_y:
             # one-hot / soft targets: the kernel reads the epoch-ordered [n, K] rows in place
             # at the device cursor (self.labels: the 0 / -1 row validity gather_batch wrote)
-            H.softmax_xent_dense(self.logits, self.y_ep, self.K, 1.0 / self.global_batch, self.dlogits,
+            H.softmax_xent_dense(self.logits, feed.y_ep, self.K, 1.0 / self.global_batch, self.dlogits,
                                  self.G[self.nparam:], label_smoothing=self.label_smoothing, labels=self.labels,
-                                 ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad, weights=self.w_ep)
+                                 ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad, weights=feed.w_ep)
         else:
             H.softmax_xent(self.logits, self.labels, self.K, 1.0 / self.global_batch, self.dlogits,
                            self.G[self.nparam:], ctrl=self.ctrl, rows=ex.xent_rows, bias_grad=bias_grad,
-                           weights=self.w_ep)
+                           weights=feed.w_ep)
         if self.reg_tab is not None:
             # loss sum += R(w) per valid local row (tail[2]), before the tail leaves with
             # bucket 0's all-reduce: the SUM over replicas yields R * (global rows)
@@ -700,15 +675,8 @@ class NativeGraphEngine(Engine):
         self.graph = g
 
     def metrics(self):
-        torch.cuda.synchronize(self.device)
-        self.reducer.check_peer()
-        c = self.ctrl.cpu().tolist()
-        loss, corr, cnt = _i2f(c[C_AL]), _i2f(c[C_AC]), _i2f(c[C_AN])
-        d = max(cnt, 1.0)
-        out = {"loss": loss / d, "_count": cnt}
-        for m in self.model.compiled_metrics:
-            out[m.name] = corr / d
-        return out
+        self.sync()
+        return epoch_metrics(self.ctrl.cpu().tolist(), [m.name for m in self.model.compiled_metrics])
 
     def finish(self):
         torch.cuda.synchronize(self.device)

@@ -32,8 +32,8 @@ import torch
 
 from ..ops import hip as H
 from ..utils import logging as dlog
+from .ctrl import C_AC, C_AL, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, WORDS, i2f
 from .native_exec import PlanExec, capture
-from .native_graph import C_AL, C_AC, C_AN, C_CUR, C_GB, C_NS, C_ROW0, C_WRAP, _i2f
 from .native_params import FlatParams
 from .native_plan import (_layer_graph, _param_weights, dense_targets, layers_eligible, loss_head_ok, lower,
                           output_head, regularizers_ok)
@@ -137,26 +137,15 @@ class NativeInference:
         rows = x.reshape(n, h * w * c)
         if not u8:
             rows = rows.astype(np.float32, copy=False)
-        dt = torch.uint8 if u8 else torch.float32
-        realloc = False
-        cap = self._bufs.get("x")
-        if cap is None or cap.dtype != dt or cap.shape[0] < n:
-            self._bufs["x"] = torch.empty((max(n, 1), h * w * c), dtype=dt, device=self.device)
-            realloc = True
+        self._grow("x", n, (h * w * c,), torch.uint8 if u8 else torch.float32)
         self._bufs["x"][:n].copy_(torch.from_numpy(np.ascontiguousarray(rows)), non_blocking=False)
-        yb = self._bufs.get("y")
-        if yb is None or yb.shape[0] < n:
-            self._bufs["y"] = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
-            realloc = True
+        self._grow("y", n, (), torch.int32)
         if y is not None and dense:
             y = np.asarray(y)
             if y.ndim != 2 or y.shape[1] != self.K:
                 raise ValueError(f"{type(self.model.loss).__name__} takes one-hot / dense targets of shape "
                                  f"(n, {self.K}) for this model, got y of shape {tuple(y.shape)}")
-            yd = self._bufs.get("yd")
-            if yd is None or yd.shape[0] < n:
-                self._bufs["yd"] = torch.zeros((max(n, 1), self.K), dtype=torch.float32, device=self.device)
-                realloc = True
+            self._grow("yd", n, (self.K,), torch.float32)
             self._bufs["yd"][:n].copy_(torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)))
             self._bufs["y"].zero_()
         elif y is not None:
@@ -165,21 +154,20 @@ class NativeInference:
             sw = np.ascontiguousarray(np.asarray(sw, dtype=np.float32).reshape(-1))
             if sw.shape[0] != n:
                 raise ValueError(f"sample_weight has length {sw.shape[0]} but there are {n} samples")
-            wb = self._bufs.get("w")
-            if wb is None or wb.shape[0] < n:
-                self._bufs["w"] = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
-                realloc = True
+            self._grow("w", n, (), torch.float32)
             self._bufs["w"][:n].copy_(torch.from_numpy(sw))
-        ob = self._bufs.get("out")
-        if ob is None or ob.shape[0] < n:
-            self._bufs["out"] = torch.zeros((max(n, 1), self.K), dtype=torch.float32, device=self.device)
-            realloc = True
-        if realloc:
-            self._graphs.clear()
+        self._grow("out", n, (self.K,), torch.float32)
         return n
 
+    def _grow(self, key, n, tail, dtype):
+        """Room for n rows in the (grown-only) buffer ``key``; a reallocation drops the graphs."""
+        b = self._bufs.get(key)
+        if b is None or b.dtype != dtype or b.shape[0] < n:
+            self._bufs[key] = torch.zeros((max(n, 1),) + tail, dtype=dtype, device=self.device)
+            self._graphs.clear()
+
     def _ctrl_reset(self, n):
-        c = torch.zeros(32, dtype=torch.int32)
+        c = torch.zeros(WORDS, dtype=torch.int32)
         c[C_NS], c[C_GB], c[C_ROW0], c[C_CUR], c[C_WRAP] = n, self.B, 0, 0, 0
         self.ctrl.copy_(c.to(self.device))
         self.tail.zero_()
@@ -223,14 +211,14 @@ class NativeInference:
                 self._graphs.pop("evaluate_dense_w", None)
         self._run(("evaluate_dense" if dense else "evaluate") + ("_w" if sample_weight is not None else ""), n)
         c = self.ctrl.cpu().tolist()
-        loss, cnt = _i2f(c[C_AL]), _i2f(c[C_AN])
+        loss, cnt = i2f(c[C_AL]), i2f(c[C_AN])
         p = self.params
         if p.reg_tab is not None:
             # the weights are static during the call: every row's loss gains the same R
             H.reg_penalty(p.P, p.reg_tab, p.reg_scratch)
             torch.cuda.synchronize(self.device)
             loss += float(p.reg_scratch[-1]) * cnt
-        return loss, cnt, _i2f(c[C_AC])
+        return loss, cnt, i2f(c[C_AC])
 
 
 def plan_for(model, batch: int, device, evaluate: bool = False):

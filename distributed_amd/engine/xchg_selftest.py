@@ -25,54 +25,64 @@ transport's result on that rank (default rank 1), to exercise the fallback.
 from __future__ import annotations
 
 import os
-import struct
-from typing import Optional, Tuple
+from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 import torch
 
 from ..utils import logging as dlog
+from .convnet_buffers import NCONV, NPARAM, OFF_B1, OFF_W1, ConvNetBuffers
+from .ctrl import C_AL, C_AN, C_GB, C_NS, C_ROW0, C_WRAP, hparam_words, rmw
 
-NPARAM, NGRAD, NCONV, FEAT, HID = 347146, 347152, 320, 5408, 64
-OFF_W1, OFF_B1 = NCONV, NCONV + FEAT * HID
-C_LR, C_MOM, C_NEST, C_NS, C_ROW0, C_GB, C_WRAP = 0, 1, 2, 3, 4, 5, 13
-C_AL, C_AC, C_AN = 10, 11, 12
 STEPS = 3
 TIMEOUT_S = 10.0
 
 
-def _f2i(f: float) -> int:
-    return struct.unpack("<i", struct.pack("<f", float(f)))[0]
+def choose_exchange(mode: str, world: int, exclude: Iterable[str], have_rccl: bool, selftested: bool, tune: bool,
+                    verify: Callable[[str], bool], time: Callable[[str], Optional[float]]):
+    """Which transport carries the fused step's gradient exchange: ``(chosen, verified,
+    fallback_from, transport_us)``.  ``mode``: DAMD_ALLREDUCE (auto | sharded | xgmi);
+    ``exclude``: transports a mid-run fault was detected on; ``selftested`` / ``tune``:
+    DAMD_XCHG_SELFTEST / DAMD_XCHG_TUNE.  ``verify(kind) -> bool`` and ``time(kind) -> seconds
+    | None`` are COLLECTIVES (``verify`` / ``time_transport`` below), so the calls depend on
+    nothing but the arguments and the callbacks' (voted) results.  Each candidate is verified
+    in order (without tuning, up to the first that passes); with tuning (auto mode only) every
+    one that passed, and RCCL, is timed the way bench.py times its window and the fastest
+    carries the run (reference README.md:398, communication = AUTO).  ``chosen`` None: nothing
+    passed.  ``verified`` True: a self-tested device exchange was chosen, else None."""
+    exclude = set(exclude)
+    cands = [k for k in ((["xgmi-sharded"] if mode in ("auto", "sharded") and world <= 8 else [])
+                         + ([] if mode == "sharded" else ["xgmi-peer"])) if k not in exclude]
+    tune = tune and mode == "auto"
+    passed, fallback_from, transport_us = [], [], {}
+    for kind in cands:  # (self-test off: every candidate counts as passed)
+        if not selftested or verify(kind):
+            passed.append(kind)
+            if not tune:
+                break
+        else:
+            fallback_from.append(kind)
+    chosen = passed[0] if passed else None
+    timed = passed + (["rccl"] if have_rccl else [])
+    if tune and len(timed) > 1:
+        for kind in timed:
+            t = time(kind)
+            if t is not None:
+                transport_us[kind] = round(t * 1e6, 2)
+        if transport_us:
+            chosen = min(transport_us, key=transport_us.get)
+    verified = True if selftested and chosen is not None and chosen != "rccl" else None
+    return chosen, verified, fallback_from, transport_us
 
 
-class _Scratch:
-    """One scratch trainer + buffers (what FusedConvNetEngine allocates), starting at P0."""
+class _Scratch(ConvNetBuffers):
+    """One scratch trainer + its buffers, starting at P0."""
 
     def __init__(self, C, dev, B, GB, rank, P0, X, Y, ppb, PP, wrap=0):
-        f32 = dict(dtype=torch.float32, device=dev)
-        BP = (B + 63) // 64 * 64
-        self.P = P0.clone()
-        self.G = torch.zeros(NGRAD, **f32)
-        self.V = torch.zeros(NGRAD, **f32)
-        self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-        self.w1alt = torch.zeros(FEAT * HID, **f32)
-        self.v1alt = torch.zeros(FEAT * HID, **f32)
-        self.w1bf = self.P[OFF_W1:OFF_B1].to(torch.bfloat16)
-        self.pooled = torch.zeros(FEAT, BP, dtype=torch.bfloat16, device=dev)
-        self.code = torch.zeros(B, FEAT, dtype=torch.uint8, device=dev)
-        self.hacc = torch.zeros(C.convnet_hacc_elems(B), dtype=torch.int64, device=dev)
-        self.hconv = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)
-        self.calt = torch.zeros(2 * NCONV, **f32)
+        super().__init__(C, dev, B, PP, P0=P0)
         self.hred = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)
-        c = torch.zeros(32, dtype=torch.int32)
-        c[C_LR], c[C_MOM], c[C_NEST] = _f2i(0.1), _f2i(0.9), 0
-        c[C_NS], c[C_ROW0], c[C_GB], c[C_WRAP] = X.shape[0], rank * B, GB, int(wrap)
-        self.ctrl.copy_(c.to(dev))
-        bufs = dict(params=self.P.data_ptr(), grads=self.G.data_ptr(), velocity=self.V.data_ptr(),
-                    ctrl=self.ctrl.data_ptr(), pooled=self.pooled.data_ptr(), code=self.code.data_ptr(),
-                    w1alt=self.w1alt.data_ptr(), v1alt=self.v1alt.data_ptr(), w1bf=self.w1bf.data_ptr(),
-                    hacc=self.hacc.data_ptr(), hconv=self.hconv.data_ptr(), calt=self.calt.data_ptr(),
-                    eager_w1=0, ppb=ppb)
+        rmw(self.ctrl, {**hparam_words(0.1, 0.9), C_NS: X.shape[0], C_ROW0: rank * B, C_GB: GB, C_WRAP: int(wrap)})
+        bufs = self.trainer_args(ppb)
         torch.cuda.synchronize(dev)
         self.t = C.ConvNetTrainer(dev.index or 0, bufs, B, PP, 1)
         self.t.set_data(X.data_ptr(), Y.data_ptr(), 1)

@@ -18,6 +18,9 @@ def main():
     nocu = os.environ.get("DIAG_NOCU") == "1"
     from distributed_amd.native import require_C
 
+    from distributed_amd.engine.convnet_buffers import exchange_capacity
+    from distributed_amd.engine.ctrl import C_IT, C_TICKET, C_XCNT
+
     C = require_C()
     dev = torch.device("cuda", 0)
     import distributed_amd as tf
@@ -32,8 +35,7 @@ def main():
     B = 64 // W
     ranks = [T.Rank(C, dev, B, 64, r, P0, X, Y, 0.1, 0.9, 1) for r in range(W)]
     NU = 4 * C.convnet_num_slices(1)
-    cap = max(W * NU * 2048, 347648 + 2 * 8 * 1408 + 16384 + T.FEAT * T.HID // 2)
-    peers = [C.PeerAllreduce(W, r, 0, cap, 16, 3.0) for r in range(W)]
+    peers = [C.PeerAllreduce(W, r, 0, exchange_capacity(C, W, 3, 1, True), 16, 3.0) for r in range(W)]
     for p in peers:
         p.link_local(peers)
     for r, rk in enumerate(ranks):
@@ -46,8 +48,8 @@ def main():
     ok = [rk.t.sync(60.0) for rk in ranks]
     print("synced", ok, flush=True)
     for r, p in enumerate(peers):
-        print("rank", r, "status", p.status(), "iters", int(ranks[r].ctrl[7]), "xcnt", int(ranks[r].ctrl[21]),
-              "ticket", int(ranks[r].ctrl[23]), flush=True)
+        print("rank", r, "status", p.status(), "iters", int(ranks[r].ctrl[C_IT]), "xcnt", int(ranks[r].ctrl[C_XCNT]),
+              "ticket", int(ranks[r].ctrl[C_TICKET]), flush=True)
     kx = 347648 + 2 * 8 * 1408
     for r, p in enumerate(peers):
         f = np.array(p.peek_out(kx, NU * 18 + 16), dtype=np.int64)

@@ -73,6 +73,7 @@ def time_steps(batch, steps, rounds, warmup):
 
 
 def time_kernels(batch, launches, rounds, warmup):
+    from distributed_amd.engine.ctrl import C_CUR3, WORDS
     from distributed_amd.ops import hip as H
 
     dev = torch.device("cuda:0")
@@ -81,8 +82,8 @@ def time_kernels(batch, launches, rounds, warmup):
                                                 (H.AUG_FLIP, 1, 0, 0, 0, 12)], 32),
         "augment_imagenet_crop_flip": (256, 4, [(H.AUG_CROP, 224, 224, 0, 0, 11), (H.AUG_FLIP, 1, 0, 0, 0, 12)], 224),
     }
-    ctrl = torch.zeros(32, dtype=torch.int32)
-    ctrl[15] = 1
+    ctrl = torch.zeros(WORDS, dtype=torch.int32)
+    ctrl[C_CUR3] = 1
     ctrl = ctrl.to(dev)
     labels = torch.zeros(batch, dtype=torch.int32, device=dev)
     graphs, nbytes = {}, {}

@@ -19,7 +19,6 @@ import argparse
 import json
 import os
 import statistics
-import struct
 import sys
 import time
 
@@ -102,6 +101,7 @@ def _time(g, launches):
 def time_kernels(launches, rounds, warmup):
     """reg_penalty and opt_step (table on / off) over ResNet-18's flat buffer and table."""
     import distributed_amd as tf
+    from distributed_amd.engine.ctrl import C_CUR3, C_LR, WORDS, f2i
     from distributed_amd.engine.native_plan import _pad8, reg_rows
     from distributed_amd.native import require_C
     from distributed_amd.ops import hip as H
@@ -120,9 +120,8 @@ def time_kernels(launches, rounds, warmup):
     V = torch.zeros(n, device=dev)
     Pb = torch.zeros(n, dtype=torch.bfloat16, device=dev)
     dummy = torch.zeros(8, device=dev)
-    ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-    ctrl[0] = struct.unpack("<i", struct.pack("<f", 1e-4))[0]
-    ctrl[15] = 1
+    ctrl = torch.zeros(WORDS, dtype=torch.int32, device=dev)
+    ctrl[C_LR], ctrl[C_CUR3] = f2i(1e-4), 1
     tail = torch.zeros(8, device=dev)
     scratch = H.reg_scratch(n, dev)
 

@@ -23,7 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 GOLDEN = os.path.join(ROOT, "tests", "golden", "convnet_step_digests.json")
 B, ROWS, SEED = 64, 256, 1234
 CONFIGS = [(u8, opt) for u8 in (True, False) for opt in ("sgd", "nesterov")]
-C_AL, C_AC, C_AN = 10, 11, 12  # ctrl words: epoch loss sum, correct, count (fp32 bits)
 
 
 def config_id(u8: bool, opt: str) -> str:
@@ -45,6 +44,8 @@ def _data(u8: bool):
 
 def _snapshot(eng, model) -> dict:
     import torch
+
+    from distributed_amd.engine.ctrl import C_AC, C_AL, C_AN  # epoch loss sum, correct, count (fp32 bits)
 
     eng.sync()  # (applies the pending update; the forward's outputs stay as step k left them)
     d = {"pooled": _sha(eng.pooled.view(torch.int16).cpu().numpy()), "code": _sha(eng.code.cpu().numpy())}

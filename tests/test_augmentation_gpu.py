@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import distributed_amd as tf
+from distributed_amd.engine.ctrl import C_CUR3, C_ROW0
 from distributed_amd.ops import hip as H
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def _out_hw(stages, h, w):
 
 def _ctrl(t, row0):
     c = torch.zeros(32, dtype=torch.int32)
-    c[4], c[15] = row0, t  # Ctrl::row0, Ctrl::cur3
+    c[C_ROW0], c[C_CUR3] = row0, t
     return c.cuda()
 
 

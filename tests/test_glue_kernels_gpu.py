@@ -19,13 +19,14 @@ import numpy as np
 import pytest
 import torch
 
+from distributed_amd.engine.ctrl import (C_AC, C_AL, C_AN, C_CUR, C_CUR3, C_GB, C_IT, C_LR, C_MOM, C_NEST, C_NS, C_ROW0,
+                                         C_WRAP)
 from distributed_amd.ops import reference as ref
 
 dev = torch.device("cuda:0") if torch.cuda.is_available() else None
 
 # words of the device control block (csrc/include/damd_common.h Ctrl)
-C_LR, C_MOM, C_NEST, C_NS, C_ROW0, C_GB, C_CUR, C_IT, C_WRAP, C_CUR3 = 0, 1, 2, 3, 4, 5, 6, 7, 13, 15
-C_ACC = (10, 11, 12)  # acc_loss, acc_correct, acc_count
+C_ACC = (C_AL, C_AC, C_AN)  # acc_loss, acc_correct, acc_count
 
 GUARD = 64
 BF_SENT = 0x7FC0

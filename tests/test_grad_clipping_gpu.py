@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import distributed_amd as tf
+from distributed_amd.engine.ctrl import C_CUR3, C_IT
 from distributed_amd.ops import hip as H
 from distributed_amd.ops import reference as R
 
@@ -124,7 +125,7 @@ class _Flat(TR._Flat):
     """test_regularizers_gpu's opt_step state with the clipping arguments."""
 
     def step(self, t, g, table=None, splits=None, **clip):
-        self.ctrl[15] = t
+        self.ctrl[C_CUR3] = t
         G = g.to(dev)
         cuts = [0] + list(splits or []) + [self.n]
         for k, (lo, hi) in enumerate(zip(cuts, cuts[1:])):
@@ -174,7 +175,7 @@ def test_opt_step_clip_modes_match_reference(name, mode, reg):
         seen |= {bool(s < 1.0) for s in scales} if scales else set((gh != before).unique().tolist())
         opt_h.apply_flat(ph, gh)
         torch.testing.assert_close(one.P.cpu(), ph, rtol=1e-5, atol=1e-6)
-        assert int(one.ctrl[7]) == t
+        assert int(one.ctrl[C_IT]) == t
         for i, nm in enumerate(one.names):
             if nm:
                 torch.testing.assert_close(one.S[i].cpu(), opt_h.slots[nm], rtol=1e-5, atol=1e-7)

@@ -8,6 +8,7 @@ sums (1e-5, 1e-6), fp32 outputs (1e-4, 1e-5)."""
 import pytest
 import torch
 
+from distributed_amd.engine.ctrl import C_CUR, C_GB, C_NS, C_ROW0, C_WRAP
 from distributed_amd.ops import reference as ref
 
 pytestmark = pytest.mark.gpu
@@ -15,8 +16,6 @@ pytestmark = pytest.mark.gpu
 dev = torch.device("cuda:0") if torch.cuda.is_available() else None
 
 SHAPES = [(5, 10, 16), (7, 1024, 1024), (64, 1000, 1000), (3, 1500, 1504)]
-# words of the device control block (csrc/include/damd_common.h Ctrl)
-C_NS, C_ROW0, C_GB, C_CUR, C_WRAP = 3, 4, 5, 6, 13
 
 
 @pytest.fixture(scope="module")

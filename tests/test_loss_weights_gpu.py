@@ -8,6 +8,7 @@ for these kernels: bf16 gradients (1e-2, 4e-3), fp32 sums (1e-5, 1e-6)."""
 import pytest
 import torch
 
+from distributed_amd.engine.ctrl import C_CUR, C_GB, C_NS, C_ROW0, C_WRAP
 from distributed_amd.ops import reference as ref
 
 pytestmark = pytest.mark.gpu
@@ -18,8 +19,6 @@ SHAPES = [(5, 10, 16), (7, 1024, 1024), (3, 1500, 1504)]
 KINDS = ["sparse", "dense"]
 WEIGHTS = [0.0, 0.25, 1.0, 3.5, 0.5, 2.0, 1.5]  # distinct per row; row 0 has weight 0
 EPS = 0.1  # the dense kernel's label smoothing
-# words of the device control block (csrc/include/damd_common.h Ctrl)
-C_NS, C_ROW0, C_GB, C_CUR, C_WRAP = 3, 4, 5, 6, 13
 
 
 @pytest.fixture(scope="module")

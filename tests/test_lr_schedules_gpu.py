@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import distributed_amd as tf
+from distributed_amd.engine.ctrl import C_CUR3, C_IT, C_LR
 from distributed_amd.ops import hip as H
 from distributed_amd.ops import reference as R
 
@@ -30,7 +31,7 @@ class _Flat(TR._Flat):
     """test_regularizers_gpu's opt_step state with the schedule descriptor."""
 
     def step(self, t, g, sched=None, splits=None, tab=None):
-        self.ctrl[15] = t
+        self.ctrl[C_CUR3] = t
         G = g.to(dev)
         if sched is not None:
             tab = H.lr_table(sched, dev)
@@ -47,14 +48,14 @@ class _Flat(TR._Flat):
 
 
 def _device_rates(sched, steps):
-    """The rate the bookkeeping launch stored in ctrl[0] for each step (t = step + 1)."""
+    """The rate the bookkeeping launch stored in ctrl's lr word for each step (t = step + 1)."""
     f = _Flat(torch.zeros(8), O.SGD(0.5))
     g = torch.zeros(8)
     out = []
     for k in steps:
-        f.ctrl[0] = TR._i(-1.0)  # a rate nobody computes: the launch must overwrite it
+        f.ctrl[C_LR] = TR._i(-1.0)  # a rate nobody computes: the launch must overwrite it
         f.step(k + 1, g, sched)
-        assert int(f.ctrl[7]) == k + 1
+        assert int(f.ctrl[C_IT]) == k + 1
         out.append(f.rate())
     return out
 
@@ -172,7 +173,7 @@ def test_opt_step_with_schedule_matches_reference(name):
         two.step(t, g, sched, splits=[offs[2], offs[4], offs[5] + 4096])  # as the clipvalue test splits
         opt_h.apply_flat(ph, g)
         torch.testing.assert_close(one.P.cpu(), ph, rtol=1e-5, atol=1e-6)
-        assert int(one.ctrl[7]) == t and int(two.ctrl[7]) == t
+        assert int(one.ctrl[C_IT]) == t and int(two.ctrl[C_IT]) == t
         ulp, _, bound = _bound(sched, [t - 1])
         assert one.rate() == two.rate() and abs(one.rate() - sched(t - 1)) <= bound * ulp
         for i, nm in enumerate(one.names):
@@ -212,7 +213,7 @@ def test_opt_step_rejects_bad_tables():
     for what, t in cases.items():
         with pytest.raises(RuntimeError):
             f.step(2, g, tab=t)
-        assert int(f.ctrl[7]) == 1, what  # nothing was launched
+        assert int(f.ctrl[C_IT]) == 1, what  # nothing was launched
     for a, b in zip(before, f.state()):
         np.testing.assert_array_equal(a, b)
     for s in (S.ExponentialDecay(0.1, 7.5, 0.5), S.PiecewiseConstantDecay(list(range(17)), [0.1] * 18)):

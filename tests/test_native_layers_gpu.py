@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import distributed_amd as tf
+from distributed_amd.engine.ctrl import C_CUR3, C_IT, C_LR
 from distributed_amd.ops import hip as H
 from distributed_amd.ops import reference as R
 
@@ -71,7 +72,7 @@ def test_dropout_kernel_matches_host_mask():
     ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
     outs = []
     for t in (1, 2):
-        ctrl[15] = t  # Ctrl::cur3, the step's iteration
+        ctrl[C_CUR3] = t  # Ctrl::cur3, the step's iteration
         y = torch.empty_like(x)
         H.dropout(x, y, ctrl, seed, rate)
         keep = torch.from_numpy(H.dropout_mask_reference(n, seed, t, rate)).to(dev)
@@ -104,7 +105,7 @@ def test_opt_step_kernel_matches_apply_flat(name):
     Pb = torch.empty(n, dtype=torch.bfloat16, device=dev)
     S = [torch.zeros(n, device=dev) for _ in range(3)]
     ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-    ctrl[0] = struct.unpack("<i", struct.pack("<f", opt_h.learning_rate))[0]
+    ctrl[C_LR] = struct.unpack("<i", struct.pack("<f", opt_h.learning_rate))[0]
     tail = torch.zeros(8, device=dev)
     if kind == 1:
         args = (opt_h.beta_1, opt_h.beta_2, opt_h.epsilon, 0.0, 0.0, int(opt_h.amsgrad))
@@ -114,13 +115,13 @@ def test_opt_step_kernel_matches_apply_flat(name):
         args = (0.0, 0.0, 0.0, 0.0, opt_h.momentum, int(opt_h.nesterov))
     for t in range(1, 4):
         g = torch.randn(n) * (0.1 if t % 2 else 1.0) + 0.05
-        ctrl[15] = t  # what gather_batch writes at the start of the step
+        ctrl[C_CUR3] = t  # what gather_batch writes at the start of the step
         C.opt_step(P.data_ptr(), g.to(dev).data_ptr(), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
                    Pb.data_ptr(), n, ctrl.data_ptr(), tail.data_ptr(), kind, *map(float, args[:5]), args[5],
                    torch.cuda.current_stream().cuda_stream)
         opt_h.apply_flat(ph, g)
         torch.testing.assert_close(P.cpu(), ph, rtol=1e-5, atol=1e-6)
-        assert int(ctrl[7]) == t  # iterations
+        assert int(ctrl[C_IT]) == t  # iterations
         for i, nm in enumerate(names):
             if nm:
                 torch.testing.assert_close(S[i].cpu(), opt_h.slots[nm], rtol=1e-5, atol=1e-7)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import distributed_amd as tf
+from distributed_amd.engine.ctrl import C_CUR3, C_IT, C_LR
 from distributed_amd.ops import hip as H
 from distributed_amd.ops import reference as R
 
@@ -69,7 +70,7 @@ class _Flat:
         self.Pb = torch.zeros(self.n, dtype=torch.bfloat16, device=dev)
         self.S = [torch.zeros(self.n, device=dev) for _ in range(3)]
         self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-        self.ctrl[0] = _i(opt.learning_rate)
+        self.ctrl[C_LR] = _i(opt.learning_rate)
         self.tail = torch.zeros(8, device=dev)
         if self.kind == 1:
             self.args = (opt.beta_1, opt.beta_2, opt.epsilon, 0.0, 0.0, int(opt.amsgrad))
@@ -80,7 +81,7 @@ class _Flat:
 
     def step(self, t, g, table=None, splits=None):
         """One optimizer step with gradient g; splits: launch boundaries (element offsets)."""
-        self.ctrl[15] = t
+        self.ctrl[C_CUR3] = t
         G = g.to(dev)
         cuts = [0] + list(splits or []) + [self.n]
         for k, (lo, hi) in enumerate(zip(cuts, cuts[1:])):
@@ -115,7 +116,7 @@ def test_opt_step_with_table_matches_reference(name):
         two.step(t, g, table, splits=[offs[2]])  # pointers advanced, absolute lo passed
         opt_h.apply_flat(ph, g + R.reg_grad(ph, rows))
         torch.testing.assert_close(one.P.cpu(), ph, rtol=1e-5, atol=1e-6)
-        assert int(one.ctrl[7]) == t and int(two.ctrl[7]) == t
+        assert int(one.ctrl[C_IT]) == t and int(two.ctrl[C_IT]) == t
         for i, nm in enumerate(one.names):
             if nm:
                 torch.testing.assert_close(one.S[i].cpu(), opt_h.slots[nm], rtol=1e-5, atol=1e-7)

@@ -11,62 +11,32 @@ rank after several steps and a flush (deferred update, gather), the same metric 
 every rank, and agreement with ONE rank over the whole global batch (fp32: within the
 summation-order tolerance; bf16 exchange: within the stated bf16 bound)."""
 import os
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+from distributed_amd.engine.convnet_buffers import NCONV, NGRAD, NPARAM, ConvNetBuffers, exchange_capacity
+from distributed_amd.engine.ctrl import C_AC, C_AL, C_AN, C_GB, C_IT, C_NS, C_ROW0, C_WRAP, hparam_words, i2f, rmw
+
 pytestmark = pytest.mark.gpu
 
-NPARAM, NGRAD, NCONV, FEAT, HID = 347146, 347152, 320, 5408, 64
-C_LR, C_MOM, C_NEST, C_NS, C_ROW0, C_GB, C_CUR, C_IT = 0, 1, 2, 3, 4, 5, 6, 7
-C_AL, C_AC, C_AN, C_WRAP = 10, 11, 12, 13
 
-
-def _f2i(f):
-    return struct.unpack("<i", struct.pack("<f", float(f)))[0]
-
-
-def _i2f(i):
-    return struct.unpack("<f", struct.pack("<i", int(i)))[0]
-
-
-class Rank:
-    """One rank's buffers + trainer (what FusedConvNetEngine allocates)."""
+class Rank(ConvNetBuffers):
+    """One rank's buffers + trainer."""
 
     def __init__(self, C, dev, B, GB, r, P0, X, Y, lr, mom, ppb):
-        f32 = dict(dtype=torch.float32, device=dev)
-        BP = (B + 63) // 64 * 64
-        self.P = P0.clone()
-        self.G = torch.zeros(NGRAD, **f32)
-        self.V = torch.zeros(NGRAD, **f32)
-        self.ctrl = torch.zeros(32, dtype=torch.int32, device=dev)
-        self.w1alt = torch.zeros(FEAT * HID, **f32)
-        self.v1alt = torch.zeros(FEAT * HID, **f32)
-        self.w1bf = self.P[NCONV:NCONV + FEAT * HID].to(torch.bfloat16)
-        self.pooled = torch.zeros(FEAT, BP, dtype=torch.bfloat16, device=dev)
-        self.code = torch.zeros(B, FEAT, dtype=torch.uint8, device=dev)
-        self.hacc = torch.zeros(C.convnet_hacc_elems(B), dtype=torch.int64, device=dev)
-        self.hconv = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)
-        self.calt = torch.zeros(2 * NCONV, **f32)
+        super().__init__(C, dev, B, 3, P0=P0)
         self.hred = torch.zeros(2 * NCONV, dtype=torch.int64, device=dev)
-        c = torch.zeros(32, dtype=torch.int32)
-        c[C_LR], c[C_MOM], c[C_NEST] = _f2i(lr), _f2i(mom), 0
-        c[C_NS], c[C_ROW0], c[C_GB], c[C_WRAP] = X.shape[0], r * B, GB, 0
-        self.ctrl.copy_(c.to(dev))
-        bufs = dict(params=self.P.data_ptr(), grads=self.G.data_ptr(), velocity=self.V.data_ptr(),
-                    ctrl=self.ctrl.data_ptr(), pooled=self.pooled.data_ptr(), code=self.code.data_ptr(),
-                    w1alt=self.w1alt.data_ptr(), v1alt=self.v1alt.data_ptr(), w1bf=self.w1bf.data_ptr(),
-                    hacc=self.hacc.data_ptr(), hconv=self.hconv.data_ptr(), calt=self.calt.data_ptr(),
-                    eager_w1=0, ppb=ppb)
+        rmw(self.ctrl, {**hparam_words(lr, mom), C_NS: X.shape[0], C_ROW0: r * B, C_GB: GB, C_WRAP: 0})
+        bufs = self.trainer_args(ppb)
         torch.cuda.synchronize(dev)
         self.t = C.ConvNetTrainer(dev.index or 0, bufs, B, 3, 1)
         self.t.set_data(X.data_ptr(), Y.data_ptr(), 1)
 
     def metrics(self):
         c = self.ctrl.cpu().tolist()
-        return _i2f(c[C_AL]), _i2f(c[C_AC]), _i2f(c[C_AN])
+        return i2f(c[C_AL]), i2f(c[C_AC]), i2f(c[C_AN])
 
 
 def _run(W, B, steps, gbf16, ppb, P0, X, Y, lr=0.1, mom=0.9):
@@ -77,9 +47,7 @@ def _run(W, B, steps, gbf16, ppb, P0, X, Y, lr=0.1, mom=0.9):
     GB = B * W
     ranks = [Rank(C, dev, B, GB, r, P0, X, Y, lr, mom, ppb) for r in range(W)]
     if W > 1:
-        NU = 4 * C.convnet_num_slices(ppb)
-        cap = max(W * NU * 2048, 347648 + 2 * 8 * 1408 + 16384 + FEAT * HID // 2)
-        peers = [C.PeerAllreduce(W, r, 0, cap, 16, 20.0) for r in range(W)]
+        peers = [C.PeerAllreduce(W, r, 0, exchange_capacity(C, W, 3, ppb, True), 16, 20.0) for r in range(W)]
         for p in peers:
             p.link_local(peers)
         for r, rk in enumerate(ranks):
