@@ -159,30 +159,19 @@ void register_kernel_ops(py::module_& m) {
                             mom, P_<float>(rmean), P_<float>(rvar), P_<float>(st), P_<ihipStream_t>(s)),
           "bn_finalize");
   });
-  m.def("bn_apply", [](U x, U st, U r, U st2, int res_mode, int relu, U y, long M, int C, U s) {
-    check(damd::bn_apply(P_<const u16>(x), P_<const float>(st), P_<const u16>(r), P_<const float>(st2), res_mode,
-                         relu, P_<u16>(y), M, C, P_<ihipStream_t>(s)),
-          "bn_apply");
-  });
   m.def("bn_bwd_blocks", &damd::bn_bwd_blocks);
-  m.def("bn_bwd_reduce", [](U dy, U y, int relu_mask, U x, U st, U dz, U part, int T, long M, int C, U s) {
-    check(damd::bn_bwd_reduce(P_<const u16>(dy), P_<const u16>(y), relu_mask, P_<const u16>(x), P_<const float>(st),
-                              P_<u16>(dz), P_<float>(part), T, M, C, P_<ihipStream_t>(s)),
-          "bn_bwd_reduce");
-  });
+  m.def("bn_reduce_reverse", &damd::bn_reduce_reverse);
   m.def("bn_bwd_finalize", [](U part, int T, int C, float count, U st, U dgamma, U dbeta, U co, U s) {
     check(damd::bn_bwd_finalize(P_<const float>(part), T, C, count, P_<const float>(st), P_<float>(dgamma),
                                 P_<float>(dbeta), P_<float>(co), P_<ihipStream_t>(s)),
           "bn_bwd_finalize");
   });
-  m.def("bn_bwd_apply", [](U dy, U y, int relu_mask, U x, U st, U co, U dx, long M, int C, U s) {
-    check(damd::bn_bwd_apply(P_<const u16>(dy), P_<const u16>(y), relu_mask, P_<const u16>(x), P_<const float>(st),
-                             P_<const float>(co), P_<u16>(dx), M, C, P_<ihipStream_t>(s)),
-          "bn_bwd_apply");
-  });
-  // ---- BatchNorm with the finalize in the consumer (layer_ops.h BNFin / BNBwdFin) ----
-  // fin = [acc, gamma, beta, st, rmean, rvar] pointers + [count, eps, momentum]
-  // bfin = [acc, dgamma, dbeta, co] pointers + count
+  // ---- one binding per BatchNorm launcher, two statistics carriers (ops/hip.py) ----
+  // Positional: the fp32 partials protocol (part [T][2][C]; st / co written by bn_finalize /
+  // bn_bwd_finalize).  Trailing keywords: the int64 accumulators with the finalize in the
+  // consumer (layer_ops.h BNFin / BNBwdFin); an empty list is a null pointer to the launcher.
+  // fin = [acc, gamma, beta, st, rmean, rvar] pointers + fin_v = [count, eps, momentum, reps]
+  // bfin = [acc, dgamma, dbeta, co] pointers + count, reps
   auto mkfin = [](const std::vector<U>& p, const std::vector<float>& v) {
     damd::BNFin f{};
     if (p.empty()) return f;
@@ -194,33 +183,42 @@ void register_kernel_ops(py::module_& m) {
   };
   auto mkbfin = [](const std::vector<U>& p, float count, int reps) {
     damd::BNBwdFin f{};
+    if (p.empty()) return f;
     if (p.size() != 4) throw std::invalid_argument("bfin: [acc, dgamma, dbeta, co]");
     f.acc = P_<const long long>(p[0]); f.dgamma = P_<float>(p[1]); f.dbeta = P_<float>(p[2]); f.co = P_<float>(p[3]);
     f.count = count;
     f.reps = reps;
     return f;
   };
-  m.def("bn_apply_fin", [mkfin](U x, U r, int res_mode, int relu, U y, long M, int C, std::vector<U> p1,
-                                std::vector<float> v1, std::vector<U> p2, std::vector<float> v2, U s) {
-    const damd::BNFin a = mkfin(p1, v1), b = mkfin(p2, v2);
-    check(damd::bn_apply(P_<const u16>(x), a.st, P_<const u16>(r), b.st, res_mode, relu, P_<u16>(y), M, C,
-                         P_<ihipStream_t>(s), &a, &b),
-          "bn_apply_fin");
-  });
-  m.def("bn_reduce_reverse", &damd::bn_reduce_reverse);
-  m.def("bn_bwd_reduce_acc", [](U dy, U y, int relu_mask, U x, U st, U dz, U acc, int T, long M, int C, U s,
-                                int reps) {
+  const std::vector<U> none{};
+  const std::vector<float> nonev{};
+  m.def("bn_apply", [mkfin](U x, U st, U r, U st2, int res_mode, int relu, U y, long M, int C, U s,
+                            std::vector<U> fin, std::vector<float> fin_v, std::vector<U> fin2,
+                            std::vector<float> fin2_v) {
+    const damd::BNFin a = mkfin(fin, fin_v), b = mkfin(fin2, fin2_v);
+    check(damd::bn_apply(P_<const u16>(x), P_<const float>(st), P_<const u16>(r), P_<const float>(st2), res_mode,
+                         relu, P_<u16>(y), M, C, P_<ihipStream_t>(s), fin.empty() ? nullptr : &a,
+                         fin2.empty() ? nullptr : &b),
+          "bn_apply");
+  }, py::arg("x"), py::arg("st"), py::arg("r"), py::arg("st2"), py::arg("res_mode"), py::arg("relu"), py::arg("y"),
+     py::arg("M"), py::arg("C"), py::arg("s"), py::arg("fin") = none, py::arg("fin_v") = nonev,
+     py::arg("fin2") = none, py::arg("fin2_v") = nonev);
+  m.def("bn_bwd_reduce", [](U dy, U y, int relu_mask, U x, U st, U dz, U part, int T, long M, int C, U s, U acc,
+                            int reps) {
     check(damd::bn_bwd_reduce(P_<const u16>(dy), P_<const u16>(y), relu_mask, P_<const u16>(x), P_<const float>(st),
-                              P_<u16>(dz), nullptr, T, M, C, P_<ihipStream_t>(s), P_<long long>(acc), reps),
-          "bn_bwd_reduce_acc");
-  });
-  m.def("bn_bwd_apply_fin", [mkbfin](U dy, U y, int relu_mask, U x, U st, U dx, long M, int C, std::vector<U> bp,
-                                     float count, U s, int reps) {
-    const damd::BNBwdFin f = mkbfin(bp, count, reps);
+                              P_<u16>(dz), P_<float>(part), T, M, C, P_<ihipStream_t>(s), P_<long long>(acc), reps),
+          "bn_bwd_reduce");
+  }, py::arg("dy"), py::arg("y"), py::arg("relu_mask"), py::arg("x"), py::arg("st"), py::arg("dz"), py::arg("part"),
+     py::arg("T"), py::arg("M"), py::arg("C"), py::arg("s"), py::arg("acc") = 0, py::arg("reps") = 1);
+  m.def("bn_bwd_apply", [mkbfin](U dy, U y, int relu_mask, U x, U st, U co, U dx, long M, int C, U s,
+                                 std::vector<U> bfin, float count, int reps) {
+    const damd::BNBwdFin f = mkbfin(bfin, count, reps);
     check(damd::bn_bwd_apply(P_<const u16>(dy), P_<const u16>(y), relu_mask, P_<const u16>(x), P_<const float>(st),
-                             f.co, P_<u16>(dx), M, C, P_<ihipStream_t>(s), &f),
-          "bn_bwd_apply_fin");
-  });
+                             P_<const float>(co), P_<u16>(dx), M, C, P_<ihipStream_t>(s), bfin.empty() ? nullptr : &f),
+          "bn_bwd_apply");
+  }, py::arg("dy"), py::arg("y"), py::arg("relu_mask"), py::arg("x"), py::arg("st"), py::arg("co"), py::arg("dx"),
+     py::arg("M"), py::arg("C"), py::arg("s"), py::arg("bfin") = none, py::arg("count") = 0.f, py::arg("reps") = 1);
+  // the two BatchNorms of relu(BN(x) + BN(x2)) in one launch each: accumulators only
   m.def("bn_bwd_reduce_dual_acc", [](U dy, U y, int relu_mask, U x, U x2, U st, U st2, U acc, U acc2, int T, long M,
                                      int C, U s, int reps) {
     check(damd::bn_bwd_reduce_dual(P_<const u16>(dy), P_<const u16>(y), relu_mask, P_<const u16>(x),
@@ -236,26 +234,6 @@ void register_kernel_ops(py::module_& m) {
                                   P_<u16>(dx2), M, C, P_<ihipStream_t>(s), f, f2),
           "bn_bwd_apply_dual_fin");
   });
-  m.def("bn_relu_maxpool_fwd_fin", [mkfin](U x, std::vector<int> g, U y, U arg, std::vector<U> p, std::vector<float> v,
-                                           U s) {
-    const damd::PoolGeo geo = geo_(g);
-    const damd::BNFin f = mkfin(p, v);
-    check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), f.st, geo, P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s), &f),
-          "bn_relu_maxpool_fwd_fin");
-  });
-  m.def("pool_bn_bwd_reduce_acc", [](U dpool, U arg, std::vector<int> g, U x, U st, U acc, int T, U s, int reps) {
-    check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
-                                   P_<const float>(st), nullptr, T, P_<ihipStream_t>(s), P_<long long>(acc), reps),
-          "pool_bn_bwd_reduce_acc");
-  });
-  m.def("pool_bn_bwd_apply_fin", [mkbfin](U dpool, U arg, std::vector<int> g, U x, U st, U dx, std::vector<U> bp,
-                                          float count, U s, int reps) {
-    const damd::PoolGeo geo = geo_(g);
-    const damd::BNBwdFin f = mkbfin(bp, count, reps);
-    check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), geo, P_<const u16>(x),
-                                  P_<const float>(st), f.co, P_<u16>(dx), P_<ihipStream_t>(s), &f),
-          "pool_bn_bwd_apply_fin");
-  });
   m.def("maxpool_fwd", [](U x, std::vector<int> g, U y, U arg, U s) {
     check(damd::maxpool_fwd(P_<const u16>(x), geo_(g), P_<u16>(y), P_<uint8_t>(arg), P_<ihipStream_t>(s)),
           "maxpool_fwd");
@@ -264,21 +242,30 @@ void register_kernel_ops(py::module_& m) {
     check(damd::maxpool_bwd(P_<const u16>(dy), P_<const uint8_t>(arg), geo_(g), P_<u16>(dx), P_<ihipStream_t>(s)),
           "maxpool_bwd");
   });
-  m.def("bn_relu_maxpool_fwd", [](U x, U st, std::vector<int> g, U y, U arg, U s) {
+  m.def("bn_relu_maxpool_fwd", [mkfin](U x, U st, std::vector<int> g, U y, U arg, U s, std::vector<U> fin,
+                                       std::vector<float> fin_v) {
+    const damd::BNFin f = mkfin(fin, fin_v);
     check(damd::bn_relu_maxpool_fwd(P_<const u16>(x), P_<const float>(st), geo_(g), P_<u16>(y), P_<uint8_t>(arg),
-                                    P_<ihipStream_t>(s)),
+                                    P_<ihipStream_t>(s), fin.empty() ? nullptr : &f),
           "bn_relu_maxpool_fwd");
-  });
-  m.def("pool_bn_bwd_reduce", [](U dpool, U arg, std::vector<int> g, U x, U st, U part, int T, U s) {
+  }, py::arg("x"), py::arg("st"), py::arg("g"), py::arg("y"), py::arg("arg"), py::arg("s"), py::arg("fin") = none,
+     py::arg("fin_v") = nonev);
+  m.def("pool_bn_bwd_reduce", [](U dpool, U arg, std::vector<int> g, U x, U st, U part, int T, U s, U acc, int reps) {
     check(damd::pool_bn_bwd_reduce(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
-                                   P_<const float>(st), P_<float>(part), T, P_<ihipStream_t>(s)),
+                                   P_<const float>(st), P_<float>(part), T, P_<ihipStream_t>(s), P_<long long>(acc),
+                                   reps),
           "pool_bn_bwd_reduce");
-  });
-  m.def("pool_bn_bwd_apply", [](U dpool, U arg, std::vector<int> g, U x, U st, U co, U dx, U s) {
+  }, py::arg("dpool"), py::arg("arg"), py::arg("g"), py::arg("x"), py::arg("st"), py::arg("part"), py::arg("T"),
+     py::arg("s"), py::arg("acc") = 0, py::arg("reps") = 1);
+  m.def("pool_bn_bwd_apply", [mkbfin](U dpool, U arg, std::vector<int> g, U x, U st, U co, U dx, U s,
+                                      std::vector<U> bfin, float count, int reps) {
+    const damd::BNBwdFin f = mkbfin(bfin, count, reps);
     check(damd::pool_bn_bwd_apply(P_<const u16>(dpool), P_<const uint8_t>(arg), geo_(g), P_<const u16>(x),
-                                  P_<const float>(st), P_<const float>(co), P_<u16>(dx), P_<ihipStream_t>(s)),
+                                  P_<const float>(st), P_<const float>(co), P_<u16>(dx), P_<ihipStream_t>(s),
+                                  bfin.empty() ? nullptr : &f),
           "pool_bn_bwd_apply");
-  });
+  }, py::arg("dpool"), py::arg("arg"), py::arg("g"), py::arg("x"), py::arg("st"), py::arg("co"), py::arg("dx"),
+     py::arg("s"), py::arg("bfin") = none, py::arg("count") = 0.f, py::arg("reps") = 1);
   m.def("gap_fwd", [](U x, int N, int HW, int C, U y, int y_f32, U s) {
     check(damd::gap_fwd(P_<const u16>(x), N, HW, C, P_<void>(y), y_f32, P_<ihipStream_t>(s)), "gap_fwd");
   });

@@ -4,6 +4,7 @@ with no allocation, and its forward ops; :func:`capture` records a step as a HIP
 from __future__ import annotations
 
 import gc
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -40,10 +41,29 @@ def capture(device, fn, *, stream=None, keep_graph=False):
     return g
 
 
+@dataclass
+class BNState:
+    """What a BatchNorm node carries on the device (``nd.attrs["bn_state"]``).  Its statistics
+    protocol (ops/hip.py: partials or accumulators) is decided once, by PlanExec._plan_bn_fin;
+    the ops hand ``fwd`` and ``carry()`` to ops/hip.py without looking inside."""
+    st: torch.Tensor  # [4][C] mean, invstd, scale, shift
+    co: torch.Tensor  # [3][C] backward coefficients
+    fwd: object  # what a forward consumer reads: st, or the BNFin that finalizes into it
+    fwd_part: torch.Tensor  # fp32 [T][2][C] partials the forward turns into st with a bn_finalize launch, or None
+    bwd: torch.Tensor  # the backward sums: fp32 [T][2][C] partials, or the int64 accumulator
+    carrier: str = "part"  # the H.bn_bwd / H.pool_bn_bwd argument that takes bwd: "part" or "acc"
+    dgrad: torch.Tensor = None  # bwd's like, written by the consuming conv's backprop-input (_plan_bn_dgrad_fusion)
+    dgrad_fused: bool = False  # ... and this step's backprop-input did write it
+
+    def carry(self, buf=None):
+        """The part / acc arguments of H.bn_bwd / H.pool_bn_bwd for ``buf`` (default: bwd)."""
+        return {"part": None, "acc": None, self.carrier: self.bwd if buf is None else buf}
+
+
 class PlanExec:
     """The buffers of ``plan`` on ``device`` and the forward ops over them; weights come from
     ``params`` (a FlatParams over every variable the plan reads).
-    ``bn_fin`` (with DAMD_BN_FIN, default on): BatchNorm statistics through int64 fixed-point
+    ``bn_fin`` (with DAMD_BN_FIN, default on; per node, _plan_bn_fin): BatchNorm statistics through int64 fixed-point
     accumulators (order-independent: bitwise the same sums whatever order the producer blocks
     arrive in) finalized inside the consumer kernels (ops/hip.py BNFin): 40 fewer launches per
     ResNet-18 step.  Same-address fp64 atomics serialise at the memory side (~18 ns each: with
@@ -139,11 +159,9 @@ class PlanExec:
             elif k == "BatchNormalization":
                 C = nd.out.shape[-1]
                 M = int(np.prod(nd.out.shape[:-1]))
-                nd.attrs["st"] = torch.zeros(4, C, device=dev)
-                T_ = self.C.bn_bwd_blocks(M, C)
-                nd.attrs["T"] = T_
-                nd.attrs["part"] = torch.zeros(max(T_, 1), 2, C, device=dev)
-                nd.attrs["co"] = torch.zeros(3, C, device=dev)
+                st = torch.zeros(4, C, device=dev)
+                part = torch.zeros(max(H.bn_bwd_blocks(M, C), 1), 2, C, device=dev)
+                nd.attrs["bn_state"] = BNState(st, torch.zeros(3, C, device=dev), fwd=st, fwd_part=part, bwd=part)
                 self._ident(C)  # (built here, not by the first step that needs it)
             elif k in ("Activation", "ReLU"):
                 self._ident(nd.out.shape[-1])
@@ -176,13 +194,19 @@ class PlanExec:
         self.act_bytes = nbytes
 
     def _plan_bn_fin(self):
-        """Fixed-point statistics accumulators of every BatchNorm ([2][C] forward sums, [2][C]
-        backward sums) in one buffer, cleared by the step's gather_batch launch; the conv
-        producing a BN input accumulates into it from its epilogue."""
+        """The statistics protocol of every BatchNorm (the only place that decides it).  A node
+        whose input's conv produces its statistics (stats_from_conv) gets accumulators: fixed
+        point [2][C] forward sums the conv's epilogue adds into and [2][C] backward sums, all in
+        one buffer cleared by the step's gather_batch launch.  Every other node keeps partials:
+        it sums its input itself (H.bn_stats), and that kernel cannot write the forward
+        accumulator layout."""
         bns = [nd for nd in self.plan.live if nd.kind == "BatchNormalization"]
         use = (self.bn_fin and env.get_bool("DAMD_BN_FIN", True)
                and all(nd.out.shape[-1] <= H.FIN_MAX_C for nd in bns))
         self.bn_acc = None
+        bns = [nd for nd in bns if nd.attrs.get("stats_from_conv")]
+        for nd in bns:  # (partials: the ones the conv's epilogue writes)
+            nd.attrs["bn_state"].fwd_part = self.plan.producer(nd.inputs[0]).attrs["stats_buf"]
         if not use or not bns:
             return
         R = max(1, env.get_int("DAMD_BN_REPS", 8))
@@ -193,18 +217,16 @@ class PlanExec:
         self.bn_acc = torch.zeros(tot, dtype=torch.int64, device=self.device)
         o = 0
         for nd in bns:
-            C = nd.out.shape[-1]
+            C, b, l = nd.out.shape[-1], nd.attrs["bn_state"], nd.layer
             nf, nb = 2 * C * (R + 1), 4 * C * (R + 1)
-            nd.attrs["acc_f"] = self.bn_acc[o:o + nf].view(R + 1, 2 * C)
-            nd.attrs["acc_b"] = self.bn_acc[o + nf:o + nf + nb].view(R + 1, 4 * C)
+            acc_f = self.bn_acc[o:o + nf].view(R + 1, 2 * C)
+            b.carrier, b.bwd = "acc", self.bn_acc[o + nf:o + nf + nb].view(R + 1, 4 * C)
             o += nf + nb
-            if nd.attrs.get("stats_from_conv"):
-                self.plan.producer(nd.inputs[0]).attrs["stats_buf"] = nd.attrs["acc_f"]
-            l = nd.layer
+            self.plan.producer(nd.inputs[0]).attrs["stats_buf"] = acc_f
             M = int(np.prod(nd.inputs[0].shape[:-1]))
-            nd.attrs["fin"] = H.BNFin(nd.attrs["acc_f"], self.params.view(l.gamma), self.params.view(l.beta),
-                                      nd.attrs["st"], l.moving_mean.value, l.moving_variance.value, M, l.epsilon,
-                                      l.momentum)
+            b.fwd_part = None
+            b.fwd = H.BNFin(acc_f, self.params.view(l.gamma), self.params.view(l.beta), b.st, l.moving_mean.value,
+                            l.moving_variance.value, M, l.epsilon, l.momentum)
 
     def _bn_relu_convs(self):
         """(bn, conv) of every BN -> ReLU -> Conv2D chain with an own-pass BN + ReLU, the conv
@@ -233,8 +255,9 @@ class PlanExec:
             if plan["amode"] != H.A_DGRAD3:
                 continue
             # with the in-consumer finalize the epilogue adds into the fixed-point accumulator
-            a["dgrad_part"] = (a["acc_b"] if a.get("fin") is not None else
-                               torch.zeros(plan["stats_T"], 2, bn.out.shape[-1], device=self.device))
+            b = a["bn_state"]
+            b.dgrad = (b.bwd if b.carrier == "acc" else
+                       torch.zeros(plan["stats_T"], 2, bn.out.shape[-1], device=self.device))
             conv.attrs["bnred"] = bn
 
     def _plan_bn_conv_fold(self):
@@ -248,8 +271,7 @@ class PlanExec:
             return
         for bn, conv in self._bn_relu_convs():
             a, l = bn.attrs, conv.layer
-            if (a.get("fin") is None or not a.get("stats_from_conv") or conv.attrs.get("stem4")
-                    or conv.inputs[0].root() is not bn.out.root()):
+            if a["bn_state"].carrier != "acc" or conv.attrs.get("stem4") or conv.inputs[0].root() is not bn.out.root():
                 continue
             plan = H.conv_fwd_plan(tuple(bn.out.shape), tuple(l.kernel.shape), l.strides, l.padding)
             if plan["amode"] != H.A_CONV3 or plan["splits"] != 1:
@@ -290,7 +312,7 @@ class PlanExec:
             bn = nd.attrs.get("bnin")  # BN -> ReLU of the input applied on load (_plan_bn_conv_fold)
             H.conv_fwd(bn.inputs[0].root().buf if bn is not None else x, wb, nd.out.root().buf, l.strides, l.padding,
                        bias=bias, relu=relu, stats=nd.attrs.get("stats_buf"), workspace=self.gemm_ws,
-                       bnin=(bn.attrs["fin"], x) if bn is not None else None)
+                       bnin=(bn.attrs["bn_state"].fwd, x) if bn is not None else None)
         self._act_epilogue(nd)
 
     def _fwd_DepthwiseConv2D(self, nd):
@@ -337,43 +359,19 @@ class PlanExec:
             H.act_fwd(y, y, an)
 
     def _fwd_BatchNormalization(self, nd):
-        l = nd.layer
+        l, b = nd.layer, nd.attrs["bn_state"]
         x = nd.inputs[0].root()
-        C = x.shape[-1]
-        M = int(np.prod(x.shape[:-1]))
-        st = nd.attrs["st"]
-        if self.plan.inference:
-            # the moving statistics: the owner fills st (bn_infer_st) once per call
-            if not nd.attrs.get("stats_only") and nd.attrs.get("pool") is None:
-                H.bn_apply(x.buf, st, nd.out.root().buf, relu=nd.attrs.get("relu", False))
-            return  # (else: applied by the fused Add / MaxPool that consumes it)
-        gamma = self.params.view(l.gamma)
-        beta = self.params.view(l.beta)
-        fin = nd.attrs.get("fin")
-        if fin is not None:
-            if not nd.attrs.get("stats_from_conv"):  # sum / sum of squares of x into acc_f
-                # (bn_bwd_reduce adds two words per value, replicas 4C apart: the layout it is
-                # checked against here)
-                self.C.bn_bwd_reduce_acc(x.buf.data_ptr(), 0, 0, x.buf.data_ptr(), self._ident(C).data_ptr(), 0,
-                                         nd.attrs["acc_f"].data_ptr(), nd.attrs["T"], M, C, H.stream_handle(),
-                                         H.acc_reps(nd.attrs["acc_f"], C, 4))
-            if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None or nd.attrs.get("conv_fold"):
-                return  # finalized and applied by the fused Add / MaxPool / direct conv that consumes it
-            H.bn_apply_fin(x.buf, nd.out.root().buf, fin, relu=nd.attrs.get("relu", False))
-            return
-        if nd.attrs.get("stats_from_conv"):
-            part = self.plan.producer(x).attrs["stats_buf"]
-            Tn = part.shape[0]
-        else:
-            part, Tn = nd.attrs["part"], nd.attrs["T"]
-            ident = self._ident(C)
-            self.C.bn_bwd_reduce(x.buf.data_ptr(), 0, 0, x.buf.data_ptr(), ident.data_ptr(), 0, part.data_ptr(), Tn,
-                                 M, C, H.stream_handle())
-        H.bn_finalize(part, Tn, C, M, gamma, beta, l.epsilon, l.momentum, l.moving_mean.value,
-                      l.moving_variance.value, st)
-        if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None:
-            return  # applied by the fused Add / MaxPool that consumes it
-        H.bn_apply(x.buf, st, nd.out.root().buf, relu=nd.attrs.get("relu", False))
+        # inference: the moving statistics; the owner fills st (H.bn_infer_st) once per call
+        if not self.plan.inference and b.fwd_part is not None:
+            Tn = b.fwd_part.shape[0]
+            if not nd.attrs.get("stats_from_conv"):  # sum / sum of squares of x
+                Tn = H.bn_stats(x.buf, self._ident(x.shape[-1]), b.fwd_part)
+            H.bn_finalize(b.fwd_part, Tn, x.shape[-1], int(np.prod(x.shape[:-1])), self.params.view(l.gamma),
+                          self.params.view(l.beta), l.epsilon, l.momentum, l.moving_mean.value,
+                          l.moving_variance.value, b.st)
+        if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None or nd.attrs.get("conv_fold"):
+            return  # (finalized and) applied by the fused Add / MaxPool / direct conv that consumes it
+        H.bn_apply(x.buf, b.fwd, nd.out.root().buf, relu=nd.attrs.get("relu", False))
 
     def _fwd_Activation(self, nd):
         C = nd.out.shape[-1]
@@ -407,23 +405,16 @@ class PlanExec:
         if mode == "raw":
             r, st2 = other.root().buf, None
         else:
-            r, st2 = other.inputs[0].root().buf, other.attrs["st"]
-        if main.attrs.get("fin") is not None:
-            H.bn_apply_fin(x.buf, nd.out.root().buf, main.attrs["fin"], relu=nd.attrs.get("relu", False), r=r,
-                           fin2=other.attrs["fin"] if mode == "bn" else None)
-            return
-        H.bn_apply(x.buf, main.attrs["st"], nd.out.root().buf, relu=nd.attrs.get("relu", False), r=r, st2=st2)
+            r, st2 = other.inputs[0].root().buf, other.attrs["bn_state"].fwd
+        H.bn_apply(x.buf, main.attrs["bn_state"].fwd, nd.out.root().buf, relu=nd.attrs.get("relu", False), r=r,
+                   st2=st2)
 
     def _fwd_MaxPooling2D(self, nd):
         l = nd.layer
         bn = nd.attrs.get("bn")
-        if bn is not None and bn.attrs.get("fin") is not None:
-            H.bn_relu_maxpool_fwd_fin(bn.inputs[0].root().buf, nd.out.root().buf, nd.attrs["arg"], l.pool_size,
-                                      l.strides, l.padding, bn.attrs["fin"])
-            return
         if bn is not None:  # stem fusion: pool(relu(BN(x))) straight from the conv output
-            H.bn_relu_maxpool_fwd(bn.inputs[0].root().buf, bn.attrs["st"], nd.out.root().buf, nd.attrs["arg"],
-                                  l.pool_size, l.strides, l.padding)
+            H.bn_relu_maxpool_fwd(bn.inputs[0].root().buf, bn.attrs["bn_state"].fwd, nd.out.root().buf,
+                                  nd.attrs["arg"], l.pool_size, l.strides, l.padding)
             return
         H.maxpool_fwd(nd.inputs[0].root().buf, nd.out.root().buf, nd.attrs["arg"], l.pool_size, l.strides, l.padding)
 

@@ -414,11 +414,11 @@ class NativeGraphEngine(Engine):
             bn = nd.attrs.get("bnred")
             bnred = None
             if bn is not None and not acc:
-                bnred = (bn.inputs[0].root().buf, bn.attrs["st"], bn.attrs["dgrad_part"])
+                bnred = (bn.inputs[0].root().buf, bn.attrs["bn_state"].st, bn.attrs["bn_state"].dgrad)
             fused = H.conv_dgrad(dy, wb, xt.grad, l.strides, l.padding, accumulate=acc, workspace=self.gemm_ws,
                                  bnred=bnred)
             if bn is not None:
-                bn.attrs["dgrad_fused"] = bnred is not None and fused
+                bn.attrs["bn_state"].dgrad_fused = bnred is not None and fused
 
     def _conv_wgrad(self, nd, xt, dy, ws):
         """Bias and weight gradient of conv node nd (current stream, workspace ws)."""
@@ -462,33 +462,16 @@ class NativeGraphEngine(Engine):
         gradient; optionally also writes the masked dy to dz_out.  ``mask_from_x``: the
         output is bn_apply(x, relu) with no residual, so the kernels recompute the ReLU
         mask from x (already read) instead of reading the stored output."""
-        C_ = self.C
-        s = H.stream_handle()
-        x = bn.inputs[0].root()
-        C = x.shape[-1]
-        M = int(np.prod(x.shape[:-1]))
-        st, part, co, Tn = bn.attrs["st"], bn.attrs["part"], bn.attrs["co"], bn.attrs["T"]
-        dgamma, dbeta = self.params.gview(bn.layer.gamma), self.params.gview(bn.layer.beta)
-        ym = ymask.data_ptr() if relu else 0
+        x, b = bn.inputs[0].root(), bn.attrs["bn_state"]
         mode = (2 if mask_from_x else 1) if relu else 0
-        fused = bn.attrs.get("dgrad_fused") and mode == 2 and dz_out is None
+        # the sums already written by the consuming conv's backprop-input epilogue?
+        fused = b.dgrad_fused and mode == 2 and dz_out is None
+        # (dx is None only for a BatchNorm on the plan's input, which has no conv statistics and so
+        # carries partials: an accumulator's apply never gets a null dx)
         with self._grad_into(x) as dx:
-            if bn.attrs.get("fin") is not None and dx is not None:
-                H.bn_bwd_fin(dy, ymask if relu else None, mode, x.buf, st, bn.attrs["acc_b"], co, dx, dgamma=dgamma,
-                             dbeta=dbeta, dz_out=dz_out if relu else None, reduce=not fused)
-                return
-            if fused:
-                part = bn.attrs["dgrad_part"]  # written by the consuming conv's backprop-input epilogue
-                Tn = part.shape[0]
-            else:
-                C_.bn_bwd_reduce(dy.data_ptr(), ym, mode, x.buf.data_ptr(), st.data_ptr(),
-                                 dz_out.data_ptr() if (dz_out is not None and relu) else 0, part.data_ptr(), Tn, M,
-                                 C, s)
-            C_.bn_bwd_finalize(part.data_ptr(), Tn, C, float(M), st.data_ptr(), H._ptr(dgamma), H._ptr(dbeta),
-                               co.data_ptr(), s)
-            if dx is not None:
-                C_.bn_bwd_apply(dy.data_ptr(), ym, mode, x.buf.data_ptr(), st.data_ptr(), co.data_ptr(),
-                                dx.data_ptr(), M, C, s)
+            H.bn_bwd(dy, ymask if relu else None, mode, x.buf, b.st, co=b.co, dx=dx,
+                     dgamma=self.params.gview(bn.layer.gamma), dbeta=self.params.gview(bn.layer.beta),
+                     dz_out=dz_out if relu else None, reduce=not fused, **b.carry(b.dgrad if fused else None))
 
     def _bwd_BatchNormalization(self, nd):
         if nd.attrs.get("stats_only") or nd.attrs.get("pool") is not None:
@@ -558,12 +541,13 @@ class NativeGraphEngine(Engine):
         if not env.get_bool("DAMD_BN_DUAL", True):
             return False
         xs = [b.inputs[0].root() for b in (b1, b2)]
-        if (any(b.attrs.get("fin") is None or b.attrs.get("dgrad_fused") for b in (b1, b2))
+        if (any(b.attrs["bn_state"].carrier != "acc" or b.attrs["bn_state"].dgrad_fused for b in (b1, b2))
                 or xs[0] is xs[1] or any(x.written or not x.needs_grad for x in xs)
                 or xs[0].shape != xs[1].shape or xs[0].shape[-1] % 8 or 256 % (xs[0].shape[-1] // 8)):
             return False
         with self._grad_into(xs[0]) as dx1, self._grad_into(xs[1]) as dx2:  # first writers (checked above)
-            args = [{"x": x.buf, "st": b.attrs["st"], "acc": b.attrs["acc_b"], "co": b.attrs["co"], "dx": dx,
+            args = [{"x": x.buf, "st": b.attrs["bn_state"].st, "acc": b.attrs["bn_state"].bwd,
+                     "co": b.attrs["bn_state"].co, "dx": dx,
                      "dgamma": self.params.gview(b.layer.gamma), "dbeta": self.params.gview(b.layer.beta)}
                     for b, x, dx in zip((b1, b2), xs, (dx1, dx2))]
             H.bn_bwd_fin_dual(dy, ymask if relu else None, 1 if relu else 0, args)
@@ -573,16 +557,11 @@ class NativeGraphEngine(Engine):
         l = nd.layer
         bn = nd.attrs.get("bn")
         if bn is not None:  # the whole BN(+ReLU) backward of the fused stem
-            x = bn.inputs[0].root()
-            dgamma, dbeta = self.params.gview(bn.layer.gamma), self.params.gview(bn.layer.beta)
+            x, b = bn.inputs[0].root(), bn.attrs["bn_state"]
             with self._grad_into(x) as dx:
-                if bn.attrs.get("fin") is not None and dx is not None:
-                    H.pool_bn_bwd_fin(nd.out.root().grad, nd.attrs["arg"], x.buf, bn.attrs["st"], bn.attrs["acc_b"],
-                                      bn.attrs["co"], dx, l.pool_size, l.strides, l.padding, dgamma=dgamma,
-                                      dbeta=dbeta)
-                else:
-                    H.pool_bn_bwd(nd.out.root().grad, nd.attrs["arg"], x.buf, bn.attrs["st"], bn.attrs["part"],
-                                  bn.attrs["co"], dx, l.pool_size, l.strides, l.padding, dgamma=dgamma, dbeta=dbeta)
+                H.pool_bn_bwd(nd.out.root().grad, nd.attrs["arg"], x.buf, b.st, co=b.co, dx=dx, pool=l.pool_size,
+                              strides=l.strides, padding=l.padding, dgamma=self.params.gview(bn.layer.gamma),
+                              dbeta=self.params.gview(bn.layer.beta), **b.carry())
             return
         with self._grad_into(nd.inputs[0]) as dx:
             if dx is not None:

@@ -88,12 +88,10 @@ class NativeInference:
         keep = []  # moving statistics moved to the device for this call: alive until the sync
         for nd in self._bn:
             l = nd.layer
-            C = nd.out.shape[-1]
             mean, var = (w.value.detach().to(self.device, torch.float32).contiguous()
                          for w in (l.moving_mean, l.moving_variance))
             keep += [mean, var]
-            self.C.bn_infer_st(mean.data_ptr(), var.data_ptr(), H._ptr(p.view(l.gamma)), H._ptr(p.view(l.beta)),
-                               float(l.epsilon), C, nd.attrs["st"].data_ptr(), H.stream_handle())
+            H.bn_infer_st(mean, var, p.view(l.gamma), p.view(l.beta), l.epsilon, nd.attrs["bn_state"].st)
         torch.cuda.current_stream(self.device).synchronize()
 
     # --- the step ---------------------------------------------------------------------------

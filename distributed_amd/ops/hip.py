@@ -592,7 +592,7 @@ def conv_fwd(x, w, out, strides=(1, 1), padding="valid", bias=None, relu=False, 
     (BN batch statistics partials) must have conv_fwd_plan(...)["stats_T"] rows.
     bnin = (fin: BNFin, y): x is a BatchNorm's input and the conv runs on y = relu(BN(x)),
     finalized and applied on load by the direct kernel (A_CONV3 plans only), which also
-    stores y (bitwise bn_apply_fin(x, y, fin, relu=True)) and publishes fin's st / moving
+    stores y (bitwise bn_apply(x, fin, y, relu=True)) and publishes fin's st / moving
     statistics."""
     n, h, wd, cin, ho, wo, kh, kw, s, pad, cout = conv_geo(x.shape, w.shape, strides, padding)
     _chk(x, torch.bfloat16, "x")
@@ -730,81 +730,18 @@ def conv_wgrad(x, dy, dw, strides=(1, 1), padding="valid", workspace: Optional[t
                   geo=(h, wd, cin, ho, wo, kh, kw, s, pad), accumulate=accumulate)
 
 
-# ---- BN / pooling / loss / optimizer -------------------------------------------------------------
-def bn_finalize(part, T, C, count, gamma, beta, eps, momentum, rmean, rvar, st):
-    _C().bn_finalize(_ptr(part), T, C, float(count), _ptr(gamma), _ptr(beta), float(eps), float(momentum),
-                     _ptr(rmean), _ptr(rvar), _ptr(st), stream_handle())
-
-
-def bn_apply(x, st, y, relu=False, r=None, st2=None):
-    C = x.shape[-1]
-    M = x.numel() // C
-    mode = 0 if r is None else (1 if st2 is None else 2)
-    _C().bn_apply(_ptr(x), _ptr(st), _ptr(r), _ptr(st2), mode, int(relu), _ptr(y), M, C, stream_handle())
-
-
-def bn_bwd(dy, y, relu_mask, x, st, part, co, dx, dgamma=None, dbeta=None, dz_out=None):
-    """Full BN backward (reduce, finalize, apply); part must hold bn_bwd_blocks(M, C) x 2C."""
-    C = x.shape[-1]
-    M = x.numel() // C
-    T = _C().bn_bwd_blocks(M, C)
-    assert part.numel() >= T * 2 * C
-    s = stream_handle()
-    _C().bn_bwd_reduce(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dz_out), _ptr(part), T, M, C, s)
-    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
-    _C().bn_bwd_apply(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(co), _ptr(dx), M, C, s)
-
-
-def pool_geo(x_shape, pool, strides, padding):
-    n, h, w, c = x_shape
-    if padding == "same":
-        ho, pt, _ = same_pad(h, pool[0], strides[0])
-        wo, pl, _ = same_pad(w, pool[1], strides[1])
-    else:
-        ho, pt = (h - pool[0]) // strides[0] + 1, 0
-        wo, pl = (w - pool[1]) // strides[1] + 1, 0
-    return [n, h, w, c, pool[0], pool[1], strides[0], strides[1], pt, pl, ho, wo]
-
-
-def maxpool_fwd(x, y, arg, pool, strides, padding):
-    g = pool_geo(x.shape, pool, strides, padding)
-    _C().maxpool_fwd(_ptr(x), g, _ptr(y), _ptr(arg), stream_handle())
-
-
-def maxpool_bwd(dy, arg, dx, pool, strides, padding):
-    g = pool_geo(dx.shape, pool, strides, padding)
-    _C().maxpool_bwd(_ptr(dy), _ptr(arg), g, _ptr(dx), stream_handle())
-
-
-def bn_relu_maxpool_fwd(x, st, y, arg, pool, strides, padding):
-    """y, arg = maxpool(relu(BN_st(x))) without materialising the BN output (stem fusion)."""
-    g = pool_geo(x.shape, pool, strides, padding)
-    _C().bn_relu_maxpool_fwd(_ptr(x), _ptr(st), g, _ptr(y), _ptr(arg), stream_handle())
-
-
-def pool_bn_bwd(dpool, arg, x, st, part, co, dx, pool, strides, padding, dgamma=None, dbeta=None):
-    """Backward of bn_relu_maxpool_fwd: BN batch-statistics backward with the pool routing
-    and ReLU mask recomputed (reduce -> finalize (dgamma/dbeta) -> apply into dx)."""
-    g = pool_geo(x.shape, pool, strides, padding)
-    C = x.shape[-1]
-    M = x.numel() // C
-    T = _C().bn_bwd_blocks(M, C)
-    assert part.numel() >= T * 2 * C
-    s = stream_handle()
-    _C().pool_bn_bwd_reduce(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(part), T, s)
-    _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
-    if dx is not None:
-        _C().pool_bn_bwd_apply(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(co), _ptr(dx), s)
-
-
-# ---- BatchNorm with the finalize folded into the consumer kernel (layer_ops.h BNFin) ------
-# The producers (conv / dense GEMM epilogue with an int64 `stats` accumulator, split-K
-# finish, bn_bwd_reduce with `acc`) add their per-block partials into an int64 fixed-point
-# accumulator ([reps + 1, 2C] forward, [reps + 1, 4C] backward, acc_reps: block b into replica
-# b % reps; integer sums, so the statistics do not depend on the blocks' arrival order);
-# the consumer derives the coefficients in its prologue, so neither bn_finalize nor
-# bn_bwd_finalize is launched.  The accumulators must be zero before the producers run
-# (the native graph engine clears them all in the step's gather_batch launch).
+# ---- BatchNorm / pooling ------------------------------------------------------------------------
+# One launcher per op, two carriers of the batch statistics.  The caller names the carrier; it
+# is never guessed from a dtype.
+# * partials: producers (a GEMM epilogue with fp32 `stats`, bn_stats, bn_bwd_reduce) write fp32
+#   per-block rows part [T][2][C]; bn_finalize / bn_bwd_finalize launches turn them into st / co.
+#   Forward argument: the st tensor; backward: part.
+# * accumulators: producers (the same epilogues with an int64 `stats`, the split-K finish,
+#   bn_bwd_reduce) add into int64 fixed point ([reps + 1, 2C] forward, [reps + 1, 4C] backward,
+#   acc_reps: block b into replica b % reps; integer sums, so independent of the blocks' arrival
+#   order) and the consumer finalizes in its prologue (layer_ops.h BNFin / BNBwdFin): no finalize
+#   launch.  Forward argument: a BNFin in place of st; backward: acc.  The accumulators must be
+#   zero before the producers run (the native graph engine clears them in gather_batch).
 FIN_MAX_C = 4096
 STEM_FUSE_MAX_C = 2048  # pool.hip pool_bn_bwd_reduce: C / 8 channel groups within one 256-thread block
 
@@ -831,52 +768,101 @@ class BNFin:
         return self._p, self._v
 
 
-_NOFIN = ([], [])
+def _fwd_stats(st):
+    """(st pointer, BNFin pointers, BNFin values) of a forward statistics argument."""
+    return (_ptr(st.st), *st.args()) if isinstance(st, BNFin) else (_ptr(st), [], [])
 
 
-def bn_apply_fin(x, y, fin: BNFin, relu=False, r=None, fin2: Optional[BNFin] = None):
-    """bn_apply with its statistics finalized in the kernel: y = act(BN(x) [+ r | + BN2(r)])."""
+def _bwd_stats(part, acc, M, C, co, dgamma, dbeta, who):
+    """(reduce keywords, apply keywords) of a backward carrier: none for partials, the checked
+    accumulator (acc_reps) and what its apply finalizes into for acc."""
+    if (part is None) == (acc is None):
+        raise ValueError(f"{who}: exactly one of part (fp32 partials) and acc (int64 accumulator)")
+    if acc is None:
+        return {}, {}
+    reps = acc_reps(acc, C, 4)
+    return (dict(acc=_ptr(acc), reps=reps),
+            dict(bfin=[_ptr(acc), _ptr(dgamma), _ptr(dbeta), _ptr(co)], count=float(M), reps=reps))
+
+
+def bn_bwd_blocks(M: int, C: int) -> int:
+    return _C().bn_bwd_blocks(M, C)
+
+
+def bn_stats(x, ident, part):
+    """Sum and sum of squares of x [.., C] per channel into the fp32 partials part [T][2][C]
+    (bn_bwd_reduce against ident = rows (0, 1, 1, 0): mean 0, invstd 1); returns T.  Partials
+    only: the kernel adds into an accumulator in the backward two-word layout, which no forward
+    consumer (BNFin: one word per value) decodes."""
+    if part.dtype != torch.float32:
+        raise ValueError("bn_stats: fp32 partials (the kernel cannot write a forward accumulator)")
     C = x.shape[-1]
     M = x.numel() // C
-    mode = 0 if r is None else (1 if fin2 is None else 2)
-    p1, v1 = fin.args()
-    p2, v2 = fin2.args() if fin2 is not None else _NOFIN
-    _C().bn_apply_fin(_ptr(x), _ptr(r), mode, int(relu), _ptr(y), M, C, p1, v1, p2, v2, stream_handle())
+    T = bn_bwd_blocks(M, C)
+    assert part.numel() >= T * 2 * C
+    _C().bn_bwd_reduce(_ptr(x), 0, 0, _ptr(x), _ptr(ident), 0, _ptr(part), T, M, C, stream_handle())
+    return T
 
 
-def bn_bwd_fin(dy, y, relu_mask, x, st, acc, co, dx, dgamma=None, dbeta=None, dz_out=None, reduce=True):
-    """BN backward in two launches: bn_bwd_reduce adds sum(dz), sum(dz * xhat) into the int64
-    accumulator acc [reps + 1][4C] (two words per value, then the flag row; reduce=False: a conv
-    epilogue, E_BNRED, already did); bn_bwd_apply derives co, adds dgamma / dbeta (block 0) and
-    writes dx."""
+def bn_finalize(part, T, C, count, gamma, beta, eps, momentum, rmean, rvar, st):
+    _C().bn_finalize(_ptr(part), T, C, float(count), _ptr(gamma), _ptr(beta), float(eps), float(momentum),
+                     _ptr(rmean), _ptr(rvar), _ptr(st), stream_handle())
+
+
+def bn_infer_st(rmean, rvar, gamma, beta, eps, st):
+    """st [4][C] of the moving statistics (inference): what bn_finalize leaves for a batch."""
+    _C().bn_infer_st(_ptr(rmean), _ptr(rvar), _ptr(gamma), _ptr(beta), float(eps), st.shape[-1], _ptr(st),
+                     stream_handle())
+
+
+def bn_apply(x, st, y, relu=False, r=None, st2=None):
+    """y = act(BN(x) [+ r | + BN2(r)]); st / st2: each an fp32 [4][C] tensor or a BNFin."""
     C = x.shape[-1]
     M = x.numel() // C
-    r = acc_reps(acc, C, 4)
-    T = _C().bn_bwd_blocks(M, C)
+    mode = 0 if r is None else (1 if st2 is None else 2)
+    s1, p1, v1 = _fwd_stats(st)
+    s2, p2, v2 = _fwd_stats(st2)
+    _C().bn_apply(_ptr(x), s1, _ptr(r), s2, mode, int(relu), _ptr(y), M, C, stream_handle(), fin=p1, fin_v=v1,
+                  fin2=p2, fin2_v=v2)
+
+
+def bn_bwd(dy, y, relu_mask, x, st, part, co, dx, dgamma=None, dbeta=None, dz_out=None, acc=None, reduce=True):
+    """BN backward: dgamma / dbeta added to, dx written, the masked dy into dz_out (optional).
+    part (fp32, bn_bwd_blocks(M, C) x 2C): reduce, finalize, apply (dx None: no apply).
+    acc (int64 [reps + 1][4C]): reduce, then an apply that derives co and adds dgamma / dbeta.
+    reduce=False: a conv epilogue (E_BNRED) already wrote part's rows / added into acc."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    red, fin = _bwd_stats(part, acc, M, C, co, dgamma, dbeta, "bn_bwd")
+    by_acc = acc is not None
+    T = bn_bwd_blocks(M, C) if reduce or by_acc else part.shape[0]
     s = stream_handle()
     if reduce:
-        _C().bn_bwd_reduce_acc(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dz_out), _ptr(acc), T, M, C,
-                               s, r)
-        if dz_out is not None and relu_mask:
+        assert by_acc or part.numel() >= T * 2 * C
+        _C().bn_bwd_reduce(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dz_out), _ptr(part), T, M, C, s,
+                           **red)
+        if by_acc and dz_out is not None and relu_mask:
             # the reduce just wrote the masked gradient: the apply reads it instead of dy and
             # the mask source (one input tensor less, the same values)
             dy, y, relu_mask = dz_out, None, 0
-    _C().bn_bwd_apply_fin(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(dx), M, C,
-                          [_ptr(acc), _ptr(dgamma), _ptr(dbeta), _ptr(co)], float(M), s, r)
+    if not by_acc:
+        _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
+    if by_acc or dx is not None:  # (the accumulator's apply is also its finalize)
+        _C().bn_bwd_apply(_ptr(dy), _ptr(y), int(relu_mask), _ptr(x), _ptr(st), _ptr(co), _ptr(dx), M, C, s, **fin)
 
 
 def bn_bwd_fin_dual(dy, y, relu_mask, bns):
     """Backward of two BatchNorms fed by the same (masked) gradient dy -- the two BN inputs
     of relu(BN(x) + BN(xd)) -- in two launches instead of four (bn_bwd_reduce_dual /
     bn_bwd_apply_dual: one read of dy and the mask source y for both, bitwise the single-BN
-    launches).  bns: two dicts x, st, acc, co, dx, dgamma, dbeta."""
+    launches).  Accumulators only.  bns: two dicts x, st, acc, co, dx, dgamma, dbeta."""
     a, b = bns
     C = a["x"].shape[-1]
     M = a["x"].numel() // C
     r = acc_reps(a["acc"], C, 4)
     if b["x"].shape != a["x"].shape or acc_reps(b["acc"], C, 4) != r or relu_mask not in (0, 1):
         raise ValueError("bn_bwd_fin_dual: the two BatchNorms must match in shape and replicas")
-    T = _C().bn_bwd_blocks(M, C)
+    T = bn_bwd_blocks(M, C)
     s = stream_handle()
     _C().bn_bwd_reduce_dual_acc(_ptr(dy), _ptr(y), int(relu_mask), _ptr(a["x"]), _ptr(b["x"]), _ptr(a["st"]),
                                 _ptr(b["st"]), _ptr(a["acc"]), _ptr(b["acc"]), T, M, C, s, r)
@@ -887,24 +873,54 @@ def bn_bwd_fin_dual(dy, y, relu_mask, bns):
                                float(M), s, r)
 
 
-def bn_relu_maxpool_fwd_fin(x, y, arg, pool, strides, padding, fin: BNFin):
+def pool_geo(x_shape, pool, strides, padding):
+    n, h, w, c = x_shape
+    if padding == "same":
+        ho, pt, _ = same_pad(h, pool[0], strides[0])
+        wo, pl, _ = same_pad(w, pool[1], strides[1])
+    else:
+        ho, pt = (h - pool[0]) // strides[0] + 1, 0
+        wo, pl = (w - pool[1]) // strides[1] + 1, 0
+    return [n, h, w, c, pool[0], pool[1], strides[0], strides[1], pt, pl, ho, wo]
+
+
+def maxpool_fwd(x, y, arg, pool, strides, padding):
     g = pool_geo(x.shape, pool, strides, padding)
-    p, v = fin.args()
-    _C().bn_relu_maxpool_fwd_fin(_ptr(x), g, _ptr(y), _ptr(arg), p, v, stream_handle())
+    _C().maxpool_fwd(_ptr(x), g, _ptr(y), _ptr(arg), stream_handle())
 
 
-def pool_bn_bwd_fin(dpool, arg, x, st, acc, co, dx, pool, strides, padding, dgamma=None, dbeta=None):
+def maxpool_bwd(dy, arg, dx, pool, strides, padding):
+    g = pool_geo(dx.shape, pool, strides, padding)
+    _C().maxpool_bwd(_ptr(dy), _ptr(arg), g, _ptr(dx), stream_handle())
+
+
+def bn_relu_maxpool_fwd(x, st, y, arg, pool, strides, padding):
+    """y, arg = maxpool(relu(BN(x))) without materialising the BN output (stem fusion); st: an
+    fp32 [4][C] tensor or a BNFin."""
+    g = pool_geo(x.shape, pool, strides, padding)
+    s1, p, v = _fwd_stats(st)
+    _C().bn_relu_maxpool_fwd(_ptr(x), s1, g, _ptr(y), _ptr(arg), stream_handle(), fin=p, fin_v=v)
+
+
+def pool_bn_bwd(dpool, arg, x, st, part, co, dx, pool, strides, padding, dgamma=None, dbeta=None, acc=None):
+    """Backward of bn_relu_maxpool_fwd: BN batch-statistics backward with the pool routing and
+    ReLU mask recomputed; part / acc and the launches as bn_bwd's."""
     g = pool_geo(x.shape, pool, strides, padding)
     C = x.shape[-1]
     M = x.numel() // C
-    r = acc_reps(acc, C, 4)
-    T = _C().bn_bwd_blocks(M, C)
+    red, fin = _bwd_stats(part, acc, M, C, co, dgamma, dbeta, "pool_bn_bwd")
+    by_acc = acc is not None
+    T = bn_bwd_blocks(M, C)
+    assert by_acc or part.numel() >= T * 2 * C
     s = stream_handle()
-    _C().pool_bn_bwd_reduce_acc(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(acc), T, s, r)
-    _C().pool_bn_bwd_apply_fin(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(dx),
-                               [_ptr(acc), _ptr(dgamma), _ptr(dbeta), _ptr(co)], float(M), s, r)
+    _C().pool_bn_bwd_reduce(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(part), T, s, **red)
+    if not by_acc:
+        _C().bn_bwd_finalize(_ptr(part), T, C, float(M), _ptr(st), _ptr(dgamma), _ptr(dbeta), _ptr(co), s)
+    if by_acc or dx is not None:
+        _C().pool_bn_bwd_apply(_ptr(dpool), _ptr(arg), g, _ptr(x), _ptr(st), _ptr(co), _ptr(dx), s, **fin)
 
 
+# ---- other per-layer kernels, loss, optimizer ---------------------------------------------------
 def gap_fwd(x, y):
     n, h, w, c = x.shape
     _C().gap_fwd(_ptr(x), n, h * w, c, _ptr(y), int(y.dtype == torch.float32), stream_handle())

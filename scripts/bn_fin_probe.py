@@ -38,14 +38,14 @@ for (hw, c) in [(56, 64), (28, 128), (14, 256), (7, 512)]:
     co = torch.zeros(3, c, device=dev)
     gamma, beta = torch.ones(c, device=dev), torch.zeros(c, device=dev)
     rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
-    T = C_.bn_bwd_blocks(M, c)
+    T = H.bn_bwd_blocks(M, c)
     part = torch.zeros(T, 2, c, device=dev)
     s = H.stream_handle()
     ident = torch.zeros(4, c, device=dev)
     ident[1] = 1.0
 
     def base():
-        C_.bn_bwd_reduce(x.data_ptr(), 0, 0, x.data_ptr(), ident.data_ptr(), 0, part.data_ptr(), T, M, c, s)
+        H.bn_stats(x, ident, part)
         H.bn_finalize(part, T, c, M, gamma, beta, 1e-3, 0.99, rm, rv, st)
         H.bn_apply(x, st, out, relu=True)
 
@@ -57,13 +57,14 @@ for (hw, c) in [(56, 64), (28, 128), (14, 256), (7, 512)]:
     tb, tbb = timeit(base), timeit(bwd_base)
     print(f"{hw}x{hw}x{c} (M {M}, T {T}): partials+finalize+apply fwd {tb:6.2f} us  bwd {tbb:6.2f} us")
     for r in REPS:
-        acc = torch.zeros(r + 1, 4 * c, dtype=torch.int64, device=dev)  # (backward layout: 2 words / value; + flag plane)
-        fin = H.BNFin(acc, gamma, beta, st, rm, rv, M, 1e-3, 0.99)
-        red = lambda: C_.bn_bwd_reduce_acc(x.data_ptr(), 0, 0, x.data_ptr(), ident.data_ptr(), 0, acc.data_ptr(),
-                                           T, M, c, s, r)
-        app = lambda: H.bn_apply_fin(x, out, fin, relu=True)
-        bapp = lambda: C_.bn_bwd_apply_fin(dy.data_ptr(), 0, 2, x.data_ptr(), st.data_ptr(), out.data_ptr(), M, c,
-                                           [acc.data_ptr(), 0, 0, co.data_ptr()], float(M), s, r)
+        acc = H.acc_zeros(r, 4 * c, dev)  # (backward layout: 2 words / value; + flag plane)
+        # (the forward consumer reads its own one-word accumulator: times only, the sums stay zero)
+        fin = H.BNFin(H.acc_zeros(r, 2 * c, dev), gamma, beta, st, rm, rv, M, 1e-3, 0.99)
+        red = lambda: C_.bn_bwd_reduce(x.data_ptr(), 0, 0, x.data_ptr(), ident.data_ptr(), 0, 0, T, M, c, s,
+                                       acc=acc.data_ptr(), reps=r)
+        app = lambda: H.bn_apply(x, fin, out, relu=True)
+        bapp = lambda: C_.bn_bwd_apply(dy.data_ptr(), 0, 2, x.data_ptr(), st.data_ptr(), co.data_ptr(), out.data_ptr(),
+                                       M, c, s, bfin=[acc.data_ptr(), 0, 0, co.data_ptr()], count=float(M), reps=r)
         tr, ta, tba = timeit(red), timeit(app), timeit(bapp)
         both = timeit(lambda: (red(), app()))
         print(f"   reps {r:2d}: reduce(acc) {tr:6.2f}  apply(fin) {ta:6.2f}  bwd apply(fin) {tba:6.2f}  "

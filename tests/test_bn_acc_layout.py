@@ -82,12 +82,12 @@ def test_backward_entry_points_check_before_any_native_call(monkeypatch):
     good = H.acc_zeros(3, 4 * C, "cpu")
     for t in _bad(4).values():
         with pytest.raises(ValueError):
-            H.bn_bwd_fin(x, x, 1, x, st, t, co, x)
+            H.bn_bwd(x, x, 1, x, st, None, co, x, acc=t)
         with pytest.raises(ValueError):
-            H.pool_bn_bwd_fin(x, None, x, st, t, co, x, (3, 3), (2, 2), "same")
+            H.pool_bn_bwd(x, None, x, st, None, co, x, (3, 3), (2, 2), "same", acc=t)
         for pair in ((t, good), (good, t)):
             with pytest.raises(ValueError):
                 H.bn_bwd_fin_dual(x, x, 1, [dict(x=x, st=st, acc=a, co=co, dx=x) for a in pair])
     # a valid accumulator passes the check and goes on to the native module
     with pytest.raises(AssertionError, match="native module"):
-        H.bn_bwd_fin(x, x, 1, x, st, good, co, x)
+        H.bn_bwd(x, x, 1, x, st, None, co, x, acc=good)

@@ -578,7 +578,7 @@ def test_direct_conv3_dgrad_bnred(H, monkeypatch, n, h, cin, cout):
 def test_direct_conv3_bn_input(H, monkeypatch, n, h, cin, cout, reps):
     """Direct forward conv on a BatchNorm's INPUT (GemmArgs::bnin: statistics finalized from
     the fp64 accumulator replicas in the kernel, BN + ReLU applied to the staged halo) ==
-    bn_apply_fin + the plain direct conv, bitwise: the stored y, the conv output and its
+    bn_apply(fin) + the plain direct conv, bitwise: the stored y, the conv output and its
     statistics epilogue, the published st and the moving statistics; padding stays zero."""
     monkeypatch.setenv("DAMD_CONV3_MIN_WG", "1")
     shape = (n, h, h, cin)
@@ -603,7 +603,7 @@ def test_direct_conv3_bn_input(H, monkeypatch, n, h, cin, cout, reps):
         if fold:
             H.conv_fwd(xb, wb, out, (1, 1), "same", stats=ostat, bnin=(fin, y))
         else:
-            H.bn_apply_fin(xb, y, fin, relu=True)
+            H.bn_apply(xb, fin, y, relu=True)
             H.conv_fwd(y, wb, out, (1, 1), "same", stats=ostat)
         res.append((y, out, ostat, st, rm, rv))
     for a, b in zip(*res):

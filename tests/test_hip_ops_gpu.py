@@ -373,7 +373,8 @@ def test_bn_statistics_accumulators_are_order_independent(H):
         acc = H.acc_zeros(reps, 4 * C, dev)
         C_.bn_reduce_reverse(rev)
         try:
-            C_.bn_bwd_reduce_acc(dy.data_ptr(), 0, 0, x.data_ptr(), st.data_ptr(), 0, acc.data_ptr(), T, M, C, s, reps)
+            C_.bn_bwd_reduce(dy.data_ptr(), 0, 0, x.data_ptr(), st.data_ptr(), 0, 0, T, M, C, s, acc=acc.data_ptr(),
+                             reps=reps)
             torch.cuda.synchronize()
         finally:
             C_.bn_reduce_reverse(False)
@@ -442,7 +443,7 @@ def test_bn_accumulators_large_sums_and_sticky_nonfinite_flag(H):
                       torch.ones(C, device=dev), torch.zeros(C, device=dev)]).contiguous()
     acc = H.acc_zeros(8, 4 * C, dev)
     s = torch.cuda.current_stream().cuda_stream
-    C_.bn_bwd_reduce_acc(dy.data_ptr(), 0, 0, x.data_ptr(), st.data_ptr(), 0, acc.data_ptr(), T, M, C, s, 8)
+    C_.bn_bwd_reduce(dy.data_ptr(), 0, 0, x.data_ptr(), st.data_ptr(), 0, 0, T, M, C, s, acc=acc.data_ptr(), reps=8)
     torch.cuda.synchronize()
     got = H.bn_acc_decode(acc, words=2)
     bad = torch.zeros(2 * C, dtype=torch.bool)

@@ -528,6 +528,55 @@ def test_dual_bn_backward_is_bitwise():
     assert hd == hs
 
 
+def _bn_behind_biased_conv():
+    L = tf.keras.layers
+    return tf.keras.Sequential([
+        L.Conv2D(8, 3, padding="same", use_bias=False, input_shape=(8, 8, 8)), L.BatchNormalization(), L.ReLU(),
+        L.Conv2D(8, 3, padding="same"), L.BatchNormalization(), L.ReLU(),  # a bias: no statistics from the epilogue
+        L.GlobalAveragePooling2D(), L.Dense(10),
+    ])
+
+
+def _bn_add_of_mixed_protocols():
+    L = tf.keras.layers
+    inp = tf.keras.Input((8, 8, 8))
+    a = L.BatchNormalization()(L.Conv2D(8, 3, padding="same", use_bias=False)(inp))
+    b = L.BatchNormalization()(L.Conv2D(8, 1)(inp))  # a bias: this BN sums its input itself
+    out = L.Dense(10)(L.GlobalAveragePooling2D()(L.ReLU()(L.Add()([a, b]))))
+    return tf.keras.Model(inp, out)
+
+
+@pytest.mark.parametrize("build", [_bn_behind_biased_conv, _bn_add_of_mixed_protocols])
+def test_bn_without_conv_statistics_trains(monkeypatch, build):
+    """A BatchNorm whose statistics no conv epilogue produces (here: behind a conv with a
+    bias) keeps the partials protocol (bn_stats + bn_finalize, bn_bwd(part=...)) in a plan whose
+    other BatchNorms use the accumulators -- in the second model both kinds meet in one fused
+    Add.  One step under the defaults == DAMD_BN_FIN=0 (every BatchNorm on partials) at the
+    tolerances of test_bn_finalize_in_consumer_matches_finalize_kernels, DAMD_SPLITK_FIXUP=0
+    for the reason given there; two default runs of two momentum steps are bitwise equal."""
+    monkeypatch.setenv("DAMD_SPLITK_FIXUP", "0")
+    x, y = _data(64, (8, 8, 8), 10, seed=5)
+    tf.keras.backend.clear_session()
+    m = build()
+    m.compile(loss=tf.keras.losses.SparseCategoricalCrossentropy(from_logits=True),
+              optimizer=tf.keras.optimizers.SGD(learning_rate=0.1))
+    e = m._get_engine(32, 32)
+    assert e.name == "native_graph"
+    assert [nd.attrs["bn_state"].carrier for nd in e.nodes if nd.kind == "BatchNormalization"] == ["acc", "part"]
+    init = m.get_weights()
+    wf, hf, ef = _train(build, x, y, init, 32, 1, native=True)
+    wk, hk, ek = _train(build, x, y, init, 32, 1, native=True, extra_env={"DAMD_BN_FIN": "0"})
+    assert ef == ek == "native_graph"
+    for a, b in zip(wf, wk):
+        np.testing.assert_allclose(a, b, rtol=1e-3, atol=1e-4)
+    np.testing.assert_allclose(hf["loss"], hk["loss"], rtol=1e-5)
+    w2, h2, _ = _train(build, x, y, init, 32, 2, native=True, momentum=0.9)
+    w3, h3, _ = _train(build, x, y, init, 32, 2, native=True, momentum=0.9)
+    for a, b in zip(w2, w3):
+        np.testing.assert_array_equal(a, b)
+    assert h2 == h3
+
+
 @pytest.mark.parametrize("allreduce", [False, True])
 def test_weight_gradients_on_side_stream_are_bitwise(monkeypatch, allreduce):
     """DAMD_WGRAD_STREAM=1: every conv weight gradient (+ split-K reduce) on a side stream

@@ -319,7 +319,7 @@ def test_stem_forward_finalizes_in_its_prologue(H, shape, reps):
     fin = H.BNFin(acc, gd, bd, st, rmean, rvar, M, eps, mom)
     xb = bf(x)
     y, a = nans(out_shape(geo)), codes(out_shape(geo))
-    H.bn_relu_maxpool_fwd_fin(xb, y, a, *FIN_POOL, fin)
+    H.bn_relu_maxpool_fwd(xb, fin, y, a, *FIN_POOL)
     # several blocks: only block 0 publishes st, the others normalise from their own LDS copy
     items = n * geo[10] * geo[11] * C // (32 if geo[10] % 2 == 0 and geo[11] % 2 == 0 else 8)
     assert items > 2 * 256
@@ -358,14 +358,15 @@ def test_stem_backward_finalizes_in_its_prologue(H, shape, reps):
     acc = H.acc_zeros(reps, 4 * C, dev)
     T = C_.bn_bwd_blocks(M, C)
     assert T > reps
-    C_.pool_bn_bwd_reduce_acc(H._ptr(dpb), H._ptr(argb), list(geo), H._ptr(xb), H._ptr(stf), H._ptr(acc), T, s, reps)
+    C_.pool_bn_bwd_reduce(H._ptr(dpb), H._ptr(argb), list(geo), H._ptr(xb), H._ptr(stf), 0, T, s, acc=H._ptr(acc),
+                          reps=reps)
     assert torch.equal(H.bn_acc_decode(acc, 2), torch.from_numpy(np.concatenate([s0, s1])))
     if reps > 1:
         assert bool((acc[:-1] != 0).any(1).all())  # every replica took its blocks' share
     co, dx = nans((3, C), torch.float32), nans(shape)
     dg, db = torch.ones(C, device=dev), torch.ones(C, device=dev)
-    C_.pool_bn_bwd_apply_fin(H._ptr(dpb), H._ptr(argb), list(geo), H._ptr(xb), H._ptr(stf), H._ptr(dx),
-                             [H._ptr(acc), H._ptr(dg), H._ptr(db), H._ptr(co)], float(M), s, reps)
+    C_.pool_bn_bwd_apply(H._ptr(dpb), H._ptr(argb), list(geo), H._ptr(xb), H._ptr(stf), H._ptr(co), H._ptr(dx), s,
+                         bfin=[H._ptr(acc), H._ptr(dg), H._ptr(db), H._ptr(co)], count=float(M), reps=reps)
     assert M * C // 8 // 4 > 2 * 256  # several blocks even at one thread per 2x2 quad: LDS copies beyond block 0's
     # three fp32 roundings (the sum, the product, the quotient), 4x margin
     want = np.stack([st[2], -st[2] * s0 / M, -st[2] * s1 / M])
@@ -377,7 +378,7 @@ def test_stem_backward_finalizes_in_its_prologue(H, shape, reps):
     assert torch.equal(dx, dx2) and not torch.isnan(dx).any()
     # the wrapper the engine calls: the same two launches
     acc2, co2, dx3 = H.acc_zeros(reps, 4 * C, dev), nans((3, C), torch.float32), nans(shape)
-    H.pool_bn_bwd_fin(dpb, argb, xb, stf, acc2, co2, dx3, *FIN_POOL)
+    H.pool_bn_bwd(dpb, argb, xb, stf, None, co2, dx3, *FIN_POOL, acc=acc2)
     assert torch.equal(acc2, acc) and torch.equal(co2, co) and torch.equal(dx3, dx)
 
 
